@@ -6,6 +6,12 @@ Metric (BASELINE.json): Gpixel*channels/s of the FORWARD feature render,
   = H*W*C / t_fwd / 1e9, t_fwd = the whole rasterize_gaussians forward (preprocess -> binning -> blend),
     inputs already resident in HBM, called through the C-ABI.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line with the
+headline and what its own timed region shows (memory, per-rank times, per-stage event spacing); with `--dump-outputs DIR`
+it also writes what the last timed step returned (dump_outputs).  Every other leg below -- single view, API path, other
+arithmetics and host patterns, backward, roofline and workload statistics, the semantic consumer, configs 4 / 5, the CPU
+baselines, the num_rendered integrity check -- runs only with `--full`, in the order and form of the plain run before it.
+
 What one JSON line carries (rank 0):
   value / ms_per_step   the contract's number: K timed steps between barriers, a step = `--views` (default 4) views of
                         the scene in flight on as many HIP streams, every forward returning its num_rendered to the host
@@ -38,7 +44,7 @@ What one JSON line carries (rank 0):
   semantic_consumer     SURVEY 8(f) N1: per-view text similarities three ways (the reference's flow on this rasteriser, the
                         normalised values via the norm-plane epilogue, the unnormalised logits), N = 1 only;
   multi_gpu_configs     BASELINE configs 4 (views sharded) and 5 (Gaussians sharded, RCCL band exchange) on this job's
-                        ranks: with --extra-configs, and by default when N > 1 (after the line is complete, under a
+                        ranks: with --extra-configs, and with --full when N > 1 (after the line is complete, under a
                         watchdog);
   cpu_baseline          kind "port" (a restatement, not the reference itself, which cannot run here), implementation pure
                         PyTorch: the CPU splat the north star names (oracle/torch_splat.py): cfg1 in
@@ -73,7 +79,7 @@ os.environ.setdefault("PYTORCH_CUDA_ALLOC_CONF", os.environ["PYTORCH_HIP_ALLOC_C
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-EXTRA_TIMEOUT_S = float(os.environ.get("SGS_BENCH_EXTRA_TIMEOUT_S", "240"))   # configs 4 / 5 (bench.py --extra-configs, on by default when --gpus > 1)
+EXTRA_TIMEOUT_S = float(os.environ.get("SGS_BENCH_EXTRA_TIMEOUT_S", "240"))   # configs 4 / 5 (bench.py --extra-configs, on with --full when --gpus > 1)
 HBM_PEAK = 8.0e12        # MI355X spec (MI355X_MICROARCH.md "Chip-level parameters")
 FP32_FMA_PEAK = 157.3e12  # fp32 vector (= fp32-input MFMA) peak, same table
 BF16_MFMA_PEAK = 2.5e15   # dense bf16 MFMA peak
@@ -81,6 +87,10 @@ STAGES = ["preprocess", "scan_readback", "duplicate", "sort", "ranges", "blend_w
 EXACT = 15               # blend variant: fp32-input MFMA accumulate, bit-identical to the contract
 TWO_TERM = 14            # blend variant: round 2's two-term split (three products)
 NCAM = 8                 # cameras each view slot cycles through (a different view every step)
+# a plain run's headline warm-up lasts at least this long: the same kernel runs 5-7 % slower in the first ~0.2 s of a process's GPU
+# activity (single_view), and under --full the headline comes ~1.4 s into it, behind the single-view legs
+PLAIN_WARM_S = 1.5
+DUMP_BYTES = 16 << 20    # --dump-outputs: bytes per sampled output (feature map, radii) over all view slots
 
 
 def log(*a):
@@ -364,6 +374,46 @@ def extra_config_legs(rank, world, dev, dist, red_dev=None):
     return out
 
 
+def dump_outputs(path, out, dev):
+    """--dump-outputs DIR: what the timed path returned to its caller in the last timed step, row i = view slot i of this rank
+    (the inputs depend on the arguments alone: scene seed 0, camera (step - 1) mod NCAM of every slot).  The state buffers of
+    the tuple are not written: scratch laid out for the capacity guess, not values.  Files (float32 / float64, <= 48 MB + 8 V (C + 1) bytes):
+      num_rendered.npy         (V,)      the count each forward returned
+      radii.npy                (V, R)    every Gaussian's radius (R = P; when V P ints exceed DUMP_BYTES, a fixed sample:
+                                         radii_index.npy holds the Gaussians)
+      color_sample.npy         (V, S)    the (C, H, W) feature map at S fixed flat positions (color_index.npy)
+      color_channel_sum.npy    (V, C)    float64 sum of each channel over the whole frame: a change anywhere in the map shows
+    Positions are drawn once from torch.Generator().manual_seed(0), sorted, the same for every slot."""
+    os.makedirs(path, exist_ok=True)
+    V = len(out)
+    color0, radii0 = out[0][1], out[0][2]
+    g = torch.Generator().manual_seed(0)
+
+    def positions(n, k):
+        if k >= n:
+            return None
+        return torch.randint(0, n, (k,), generator=g).sort().values
+
+    k = min(1 << 20, DUMP_BYTES // (4 * V))   # (the index files are float64: <= 8 MB each)
+    c_idx = positions(color0.numel(), k)
+    r_idx = positions(radii0.numel(), k)
+    if c_idx is None:
+        c_idx = torch.arange(color0.numel())
+    arrays = {
+        "num_rendered": np.array([o[0] for o in out], np.float64),
+        "color_sample": torch.stack([o[1].reshape(-1).index_select(0, c_idx.to(dev)) for o in out]).cpu().numpy(),
+        "color_index": c_idx.numpy().astype(np.float64),
+        "color_channel_sum": torch.stack([o[1].sum(dim=(1, 2), dtype=torch.float64) for o in out]).cpu().numpy(),
+        "radii": torch.stack([o[2] if r_idx is None else o[2].index_select(0, r_idx.to(dev)) for o in out]).float().cpu().numpy(),
+    }
+    if r_idx is not None:
+        arrays["radii_index"] = r_idx.numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step: {', '.join(f'{n}{list(a.shape)}' for n, a in arrays.items())} "
+        f"({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB) in {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -386,8 +436,8 @@ def main():
     ap.add_argument("--fixed-camera", action="store_true",
                     help="every step renders the same camera per slot (profiling runs: per-kernel averages of ONE view)")
     ap.add_argument("--extra-configs", action="store_true",
-                    help="also time BASELINE configs 4 (views sharded) and 5 (Gaussians sharded, RCCL exchange); on by default "
-                         "when --gpus > 1")
+                    help="--full, and also time BASELINE configs 4 (views sharded) and 5 (Gaussians sharded, RCCL exchange); on with "
+                         "--full when --gpus > 1")
     ap.add_argument("--front-cus", type=int, default=int(os.environ.get("SGS_BENCH_FRONT_CUS", "0")),
                     help="compute units set aside for the views' front ends in the headline (raster.PartitionedStreams: every view slot gets a "
                          "blend stream on the other CUs and a front stream on these); 0 (default) = ordinary streams, every kernel anywhere.  Measured "
@@ -398,9 +448,19 @@ def main():
     ap.add_argument("--stream-priority", choices=("none", "split", "blend", "front"), default=os.environ.get("SGS_BENCH_STREAM_PRIORITY", "none"),
                     help="experiment (profiles/r06_stream_priority.txt): every view slot's front end on a second ordinary stream (split), with the blend "
                          "stream (blend) or the front stream (front) at high priority; none (default) = one stream per slot")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exact-arithmetic / backward legs")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (single view, API path, other arithmetics and host patterns, backward, "
+                         "roofline, semantic consumer, configs 4 / 5 when --gpus > 1, CPU baselines, integrity check); a plain run "
+                         "times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's view slots) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the exact-arithmetic / backward legs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.extra_configs:   # (a leg of --full)
+        args.full = True
     global NCAM
     if args.fixed_camera:
         NCAM = 1
@@ -558,24 +618,26 @@ def main():
 
     rank_ms = {}   # ms per step of the slowest / fastest rank in the last in_flight() (a straggler shows here)
 
-    def in_flight(variant, steps, warmup, stage_timing=False, defer=None, partitioned=True):
+    def in_flight(variant, steps, warmup, stage_timing=False, defer=None, partitioned=True, warm_s=0.0):
         nonlocal streams
         raster.set_blend_variant(variant)
         streams = part.streams if (part is not None and partitioned) else plain_streams
         for st_ in streams:
             st_.wait_stream(torch.cuda.current_stream(dev))
         try:
-            return _in_flight(variant, steps, warmup, stage_timing, defer)
+            return _in_flight(variant, steps, warmup, stage_timing, defer, warm_s)
         finally:
             torch.cuda.synchronize(dev)
             streams = plain_streams
 
-    def _in_flight(variant, steps, warmup, stage_timing, defer):
+    def _in_flight(variant, steps, warmup, stage_timing, defer, warm_s):
         out = None
-        for k in range(warmup):
+        t_w, k = time.perf_counter(), 0
+        while k < warmup or time.perf_counter() - t_w < warm_s:
             out = step(k, defer, out)   # exactly like the timed loop, so that the caching allocator reaches its steady-state
             #                footprint here, not in the timed region (a 10 GB hipMalloc in timed step 2 was a 240 ms stall,
             #                profiles/r02h_bench_default.json)
+            k += 1
         if stage_timing:   # deferred per-stage hipEvents for the timed steps only (no extra synchronisation)
             raster.get_stage_ms()
             raster.set_stage_timing(2)
@@ -587,7 +649,8 @@ def main():
         marks, mism = [], 0
         for k in range(steps):
             out = step(k, defer, out)
-            mism += sum(int(o[0] != ref_n[i][k % NCAM]) for i, o in enumerate(out))   # host ints, no device work
+            if ref_n is not None:
+                mism += sum(int(o[0] != ref_n[i][k % NCAM]) for i, o in enumerate(out))   # host ints, no device work
             marks.append(time.perf_counter())
         barrier()
         t = time.perf_counter() - t0
@@ -605,28 +668,30 @@ def main():
             log(f"variant {variant}: per-step host ms min/median/max: {per[0] * 1e3:.2f} / {per[len(per) // 2] * 1e3:.2f} / {per[-1] * 1e3:.2f}")
         return t / steps * 1e3, per[len(per) // 2] * 1e3, mism, out, retries
 
-    # ---- one view in flight (SURVEY 8(d)'s t_fwd), default arithmetic; its stage times feed the roofline
-    sv_cold, stage_ms_cold = single_view(args.variant)   # (in the first second of the process's GPU activity: see the steady-state leg behind the headline)
-    # the same through the inference entry point (what the drop-in module does under no_grad): no read-back hole in the GPU's timeline
-    sv_inference = single_view(args.variant, inference=True)[0]
-    # ... and as the product runs it: without the library's per-stage event records (instrumentation the two legs above switch on)
-    sv_untimed = single_view(args.variant, inference=True, stage_events=False)[0]
-    sv_inference["ms_median_without_stage_events"] = sv_untimed["ms_median"]
-    sv_inference["value_without_stage_events"] = sv_untimed["value"]
-    # integrity reference: every (slot, camera)'s num_rendered, rendered alone (concurrent forwards must reproduce it)
-    ref_n = []
-    for i in range(V):
-        row = []
-        for k in range(NCAM):
-            row.append(render(i, False, k)[0])
-            torch.cuda.synchronize(dev)
-        ref_n.append(row)
-    if world > 1:   # a mis-sharded run shows at a glance: every rank's device, its view numbers and their num_rendered
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, {"rank": rank, "device": f"cuda{local_rank}:{torch.cuda.get_device_name(dev)}", "host_affinity": affinity,
-                                          "views": [(rank * V + i) * NCAM for i in range(V)],
-                                          "num_rendered_first_camera": [row[0] for row in ref_n]})
-        rccl["per_rank"] = per_rank
+    ref_n = None   # (--full) integrity reference: every (slot, camera)'s num_rendered, rendered alone
+    if args.full:
+        # ---- one view in flight (SURVEY 8(d)'s t_fwd), default arithmetic; its stage times feed the roofline
+        sv_cold, stage_ms_cold = single_view(args.variant)   # (in the first second of the process's GPU activity: see the steady-state leg behind the headline)
+        # the same through the inference entry point (what the drop-in module does under no_grad): no read-back hole in the GPU's timeline
+        sv_inference = single_view(args.variant, inference=True)[0]
+        # ... and as the product runs it: without the library's per-stage event records (instrumentation the two legs above switch on)
+        sv_untimed = single_view(args.variant, inference=True, stage_events=False)[0]
+        sv_inference["ms_median_without_stage_events"] = sv_untimed["ms_median"]
+        sv_inference["value_without_stage_events"] = sv_untimed["value"]
+        # integrity reference: concurrent forwards must reproduce the serial num_rendered
+        ref_n = []
+        for i in range(V):
+            row = []
+            for k in range(NCAM):
+                row.append(render(i, False, k)[0])
+                torch.cuda.synchronize(dev)
+            ref_n.append(row)
+        if world > 1:   # a mis-sharded run shows at a glance: every rank's device, its view numbers and their num_rendered
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, {"rank": rank, "device": f"cuda{local_rank}:{torch.cuda.get_device_name(dev)}", "host_affinity": affinity,
+                                              "views": [(rank * V + i) * NCAM for i in range(V)],
+                                              "num_rendered_first_camera": [row[0] for row in ref_n]})
+            rccl["per_rank"] = per_rank
 
     # ---- what a user of the reference gets: the drop-in module, called as model/renderer.py:169-185,228 calls it
     def api_path(n=24, debug=True):
@@ -669,7 +734,8 @@ def main():
         p_.clear()
     torch.cuda.empty_cache()              # (the legs above leave their own cached blocks behind: the memory figures below are
     torch.cuda.reset_peak_memory_stats(dev)   # the headline's -- scene, resident state buffers, V feature maps)
-    ms_per_step, ms_step_median, mismatches, out, retries = in_flight(args.variant, args.steps, max(2, args.warmup), True)
+    ms_per_step, ms_step_median, mismatches, out, retries = in_flight(args.variant, args.steps, max(2, args.warmup), True,
+                                                                      warm_s=0.0 if args.full else PLAIN_WARM_S)
     raster.set_stage_timing(0)
     stage_ms_timed = raster.get_stage_ms()   # per-stream event spacing inside the timed region (queueing included)
     headline_rank_ms = dict(rank_ms)
@@ -680,8 +746,82 @@ def main():
                    f"of {C * H * W * 4 / 1e9:.2f} GB + resident geometry / binning / work-list buffers; a slot's previous map is "
                    "released before it renders again); the legs measured afterwards add their own buffers"}
     mem["per_view_slot_GB"] = round((mem["max_allocated_GB"] - mem["scene_GB"]) / V, 2)
+    res = None   # the line (rank 0)
     if rank == 0:
         log(f"torch max allocated {mem['max_allocated_GB']:.2f} GB, reserved {mem['reserved_GB']:.2f} GB")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, dev)
+        split = C >= 128 and args.variant not in (EXACT,)
+        arith = {0: "f32-equivalent (3-term bf16 splits, 6 MFMA products, f32 accumulate)", TWO_TERM: "bf16x3-split products, f32 accumulate"}.get(args.variant, f"blend variant {args.variant:#x}")
+        res = {
+            "metric": "Gpixel*channels/s forward render (1M Gauss, C=512, 968x1296)",
+            "value": world * V * H * W * C / (ms_per_step * 1e-3) / 1e9,
+            "unit": "Gpixel*channels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": (arith if split else "f32"),
+            "data": "synthetic",
+            "config": {"workload": f"{args.config}: P={P} Gaussians, C={C}, {H}x{W} forward render "
+                                   f"(BASELINE.md config 3 generator, seed 0)",
+                       "views_per_step_per_gpu": V, "hip_streams_per_gpu": V * (2 if part is not None else 1),
+                       "parallelism": f"views x{world * V}: {V} in flight per GPU on {V} HIP streams, {world} GPU(s), "
+                                      f"scene replicated, no collective",
+                       "rccl": rccl,
+                       "cameras": f"each of the {V} view slots cycles through {NCAM} cameras: a different view every step",
+                       "num_rendered": ("blocking read-back in the middle of every forward (the reference's host pattern, rasterizer_impl.cu:283)" if DEFER == "classic" else
+                                        "every forward returns its num_rendered as the reference's does (the host waits for it), after the whole frame was "
+                                        "enqueued against the stream's capacity guess: raster.rasterize_forward_inference, what the drop-in module does under "
+                                        "torch.no_grad() (a frame that outgrew the guess is rendered again; with --full every num_rendered is compared with the serial render); "
+                                        "classic_count below = rounds 1-4's headline pattern" if DEFER == "speculative" else
+                                        "deferred (SGS_OPT_DEFER_COUNT): buffers sized from the stream's previous frame, counts "
+                                        "checked on the device and on the host once per step; with --full every step's num_rendered is "
+                                        "compared with the serial render (integrity)"),
+                       "blend_variant": args.variant,
+                       "blend_arithmetic": ("fp32 MFMA, bit-exact" if not split else
+                                            "every weight, decision and integer output in contract fp32 (bit-exact); the C >= 128 "
+                                            "weighted sum with features and weights split EXACTLY into three bf16 terms each, the six "
+                                            "products with i + j <= 4 on v_mfma_f32_32x32x16_bf16 (round 5: the double-rate MFMA in the ping-pong sweep, whose workgroups own "
+                                            "their compute units -- DESIGN.md 5.10), fp32 accumulate.  tests: against the "
+                                            "exact (float64) composite it is as accurate as the oracle's fp32 fma chain (max and rms "
+                                            "of the element-wise error |x - exact| / max(|exact|, 1e-3 |pixel|_inf)); against the oracle "
+                                            "itself |out - oracle| <= 5e-6 |pixel|_inf everywhere, and the element-wise form exceeds 1e-4 "
+                                            "on < 1e-5 of the elements -- as the oracle's own chain does against the exact composite "
+                                            "(tests/test_configs_gpu.py); exact_f32 below is the bit-identical fp32-MFMA path")},
+            "ms_per_step_median": ms_step_median,
+            "host_affinity": affinity,
+            "ms_per_step_ranks": headline_rank_ms,   # slowest / fastest rank's own clock over the same timed region
+            "memory": mem,
+            "ms_per_view": ms_per_step / V,
+            "host_pattern": {"speculative": "speculative: the frame is enqueued in full against the stream's capacity guess, then the host waits for its num_rendered",
+                             "classic": "classic: the host waits for num_rendered in the middle of every forward (the reference's pattern)",
+                             True: "deferred counts"}[DEFER],
+            "cu_partition": ({"front_cus": part.front_cus, "blend_cus": part.cu_count - part.front_cus, "device_cus": part.cu_count,
+                              "note": "every view slot: blend stream confined to the blend CUs, front end (preprocess, depth sort, span partitions) "
+                                      "on a second stream confined to the front CUs (hipExtStreamCreateWithCUMask; sgs_stream_set_front); "
+                                      "shared_cus below = the same headline on ordinary streams"} if (part is not None and hasattr(part, "front_cus")) else
+                             ({"stream_priority": args.stream_priority, "note": "experiment: front ends on second ordinary streams (--stream-priority)"} if part is not None else None)),
+            "stage_ms_timed_region": dict(zip(STAGES, [round(v, 4) for v in stage_ms_timed])),
+            "integrity": {"forwards_checked": args.steps * V if ref_n is not None else 0,
+                          "num_rendered_mismatches_vs_serial": mismatches if ref_n is not None else None,
+                          "deferred_retries": retries, "note": "the serial num_rendered of every (slot, camera) is compared with --full"},
+            "full": args.full,
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+    if not args.full:   # a plain run: the headline is all it measures
+        del out
+        finish()
+        return
 
     # ---- one view in flight in STEADY STATE: the same leg as sv_cold, measured right behind the timed region (seconds of continuous GPU work).
     # Round 6: 24 forwards at the top of the process are a 40-ms window, and the sweep's duration wanders by +-3 % over a process's life on these
@@ -867,66 +1007,13 @@ def main():
                     traffic = tj.get("hbm_bytes_per_launch")
             except Exception:   # noqa: BLE001
                 traffic = None
-        split = C >= 128 and args.variant not in (EXACT,)
-        arith = {0: "f32-equivalent (3-term bf16 splits, 6 MFMA products, f32 accumulate)", TWO_TERM: "bf16x3-split products, f32 accumulate"}.get(args.variant, f"blend variant {args.variant:#x}")
-        res = {
-            "metric": "Gpixel*channels/s forward render (1M Gauss, C=512, 968x1296)",
-            "value": world * V * H * W * C / (ms_per_step * 1e-3) / 1e9,
-            "unit": "Gpixel*channels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": (arith if split else "f32"),
-            "data": "synthetic",
-            "config": {"workload": f"{args.config}: P={P} Gaussians, C={C}, {H}x{W} forward render "
-                                   f"(BASELINE.md config 3 generator, seed 0)",
-                       "views_per_step_per_gpu": V, "hip_streams_per_gpu": V * (2 if part is not None else 1),
-                       "parallelism": f"views x{world * V}: {V} in flight per GPU on {V} HIP streams, {world} GPU(s), "
-                                      f"scene replicated, no collective",
-                       "rccl": rccl,
-                       "cameras": f"each of the {V} view slots cycles through {NCAM} cameras: a different view every step",
-                       "num_rendered": ("blocking read-back in the middle of every forward (the reference's host pattern, rasterizer_impl.cu:283)" if DEFER == "classic" else
-                                        "every forward returns its num_rendered as the reference's does (the host waits for it), after the whole frame was "
-                                        "enqueued against the stream's capacity guess: raster.rasterize_forward_inference, what the drop-in module does under "
-                                        "torch.no_grad() (a frame that outgrew the guess is rendered again; every num_rendered is compared with the serial render); "
-                                        "classic_count below = rounds 1-4's headline pattern" if DEFER == "speculative" else
-                                        "deferred (SGS_OPT_DEFER_COUNT): buffers sized from the stream's previous frame, counts "
-                                        "checked on the device and on the host once per step; every step's num_rendered is "
-                                        "compared with the serial render (integrity)"),
-                       "blend_variant": args.variant,
-                       "blend_arithmetic": ("fp32 MFMA, bit-exact" if not split else
-                                            "every weight, decision and integer output in contract fp32 (bit-exact); the C >= 128 "
-                                            "weighted sum with features and weights split EXACTLY into three bf16 terms each, the six "
-                                            "products with i + j <= 4 on v_mfma_f32_32x32x16_bf16 (round 5: the double-rate MFMA in the ping-pong sweep, whose workgroups own "
-                                            "their compute units -- DESIGN.md 5.10), fp32 accumulate.  tests: against the "
-                                            "exact (float64) composite it is as accurate as the oracle's fp32 fma chain (max and rms "
-                                            "of the element-wise error |x - exact| / max(|exact|, 1e-3 |pixel|_inf)); against the oracle "
-                                            "itself |out - oracle| <= 5e-6 |pixel|_inf everywhere, and the element-wise form exceeds 1e-4 "
-                                            "on < 1e-5 of the elements -- as the oracle's own chain does against the exact composite "
-                                            "(tests/test_configs_gpu.py); exact_f32 below is the bit-identical fp32-MFMA path")},
-            "ms_per_step_median": ms_step_median,
-            "host_affinity": affinity,
-            "ms_per_step_ranks": headline_rank_ms,   # slowest / fastest rank's own clock over the same timed region
-            "memory": mem,
-            "ms_per_view": ms_per_step / V,
+        res.update({
             "single_view": sv_default,
             "single_view_cold": dict(sv_cold, note="the same leg at the top of the process, 0.4 s into its GPU activity (what rounds 1-5 reported as single_view)"),
             "single_view_inference": dict(sv_inference, note="one view in flight through raster.rasterize_forward_inference: the whole frame is "
                                           "enqueued against the stream's capacity guess before the host waits for num_rendered (what "
                                           "GaussianRasterizer does under torch.no_grad(); single_view above keeps the reference's mid-frame wait)"),
             "api_path": api,
-            "host_pattern": {"speculative": "speculative: the frame is enqueued in full against the stream's capacity guess, then the host waits for its num_rendered",
-                             "classic": "classic: the host waits for num_rendered in the middle of every forward (the reference's pattern)",
-                             True: "deferred counts"}[DEFER],
-            "cu_partition": ({"front_cus": part.front_cus, "blend_cus": part.cu_count - part.front_cus, "device_cus": part.cu_count,
-                              "note": "every view slot: blend stream confined to the blend CUs, front end (preprocess, depth sort, span partitions) "
-                                      "on a second stream confined to the front CUs (hipExtStreamCreateWithCUMask; sgs_stream_set_front); "
-                                      "shared_cus below = the same headline on ordinary streams"} if (part is not None and hasattr(part, "front_cus")) else
-                             ({"stream_priority": args.stream_priority, "note": "experiment: front ends on second ordinary streams (--stream-priority)"} if part is not None else None)),
             "shared_cus": shared_cus,
             "classic_count": classic,
             "deferred_count": deferred,
@@ -960,19 +1047,16 @@ def main():
                               "frac_of_hbm_peak": V * (bytes_blend + bytes_front) / (ms_per_step * 1e-3) / HBM_PEAK,
                               "single_view_frac_of_hbm_peak": (bytes_blend + bytes_front) / (sv_default["ms_median"] * 1e-3) / HBM_PEAK},
             "stage_ms": dict(zip(STAGES, [round(v, 4) for v in stage_ms])),
-            "stage_ms_timed_region": dict(zip(STAGES, [round(v, 4) for v in stage_ms_timed])),
             "multi_gpu_configs": None,
-            "integrity": {"forwards_checked": args.steps * V, "num_rendered_mismatches_vs_serial": mismatches,
-                          "deferred_retries": retries},
             "workload_stats": {"P_vis": p_vis, "num_rendered": num_rendered, "sum_n_t_eff": sum_neff,
                                "tiles": tiles, "sum_n_contrib": contributors},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_pytorch(scene, cam, C, W, H, n_eff_host)
             log("cpu_baseline: " + res["cpu_baseline"]["sample"])
             res["cpu_baseline_port"] = cpu_baseline_port(scene, cam, C, W, H, n_eff_host)
             log("cpu_baseline_port: " + res["cpu_baseline_port"]["sample"])
-    if args.extra_configs or world > 1:
+    if args.extra_configs or world > 1:   # (--full)
         # BASELINE configs 4 / 5 on this job's ranks, AFTER the line above is complete and under a watchdog: the RCCL band
         # exchange of config 5 has never run on more than one GPU (this pool hands out single-GPU boxes), and a collective
         # that hangs must not cost the job its headline -- after EXTRA_TIMEOUT_S rank 0 prints the line without them
@@ -992,11 +1076,7 @@ def main():
         if rank == 0:
             log("extra configs: " + json.dumps(extra_cfgs)[:600])
             res["multi_gpu_configs"] = extra_cfgs
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -150,7 +150,7 @@ def test_bench_two_ranks_control_flow_on_one_device():
     import json
     env = dict(os.environ, SGS_BENCH_TEST_ONE_DEVICE="1", SGS_BENCH_EXTRA_TIMEOUT_S="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]

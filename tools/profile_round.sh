@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): tools/profile_round.sh <tag>
 # The round's evidence in one go, everything into gpurun_out/<tag>/ (copy what is to be judged into profiles/):
-#   bench_default.json/.err            the default bench line (what the driver runs)
+#   bench_default.json/.err            bench.py --full: the headline and every leg beside it
 #   bench_views1_under_rocprof.json    bench.py --views 1 --fixed-camera under rocprofv3 --kernel-trace --stats
 #   kernel_stats_views1.txt            its per-kernel summary (avg duration of the dominant kernels = roofline.kernels_ms)
 #   frame_timeline.txt                 one forward of that run as its launch sequence with gaps
@@ -14,10 +14,10 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$tag
 mkdir -p $O
 cd $R
-python bench.py 2> $O/bench_default.err > $O/bench_default.json
+python bench.py --full 2> $O/bench_default.err > $O/bench_default.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt
-rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --views 1 --fixed-camera --no-cpu-baseline --no-extras --steps 600 --warmup 4 \
+rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --full --views 1 --fixed-camera --no-cpu-baseline --no-extras --steps 600 --warmup 4 \
 	> $O/bench_views1_under_rocprof.json 2> $O/bench_views1_under_rocprof.err
 db=$(find /tmp/kt -name "*results.db" | head -1)
 python $R/tools/rocpd_summary.py $db > $O/kernel_stats_views1.txt
