@@ -59,9 +59,9 @@ def preprocess(means3D, scales, rotations, opacities, view, proj, W, H, tanfovx,
     radius = torch.ceil(3.0 * torch.sqrt(lam))
     gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
     x0 = torch.clamp(torch.trunc((pix[:, 0] - radius) / TILE), 0, gx).long()
-    x1 = torch.clamp(torch.trunc((pix[:, 0] + radius + (TILE - 1)) / TILE), 0, gx).long()
+    x1 = torch.clamp(torch.trunc((pix[:, 0] + radius + TILE - 1) / TILE), 0, gx).long()
     y0 = torch.clamp(torch.trunc((pix[:, 1] - radius) / TILE), 0, gy).long()
-    y1 = torch.clamp(torch.trunc((pix[:, 1] + radius + (TILE - 1)) / TILE), 0, gy).long()
+    y1 = torch.clamp(torch.trunc((pix[:, 1] + radius + TILE - 1) / TILE), 0, gy).long()
     vis = (tz > 0.2) & (det != 0) & ((x1 - x0) * (y1 - y0) > 0)
     radii = torch.where(vis, radius, torch.zeros_like(radius)).to(torch.int32)
     return dict(depth=tz, pix=pix, conic=conic, opacity=opacities.reshape(-1), radii=radii,

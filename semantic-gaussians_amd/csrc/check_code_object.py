@@ -10,7 +10,10 @@ library if a check fails:
   1. every kernel that contains the x16 MFMA: 256 registers per wave, 512 threads, > 80 KB LDS, no scratch, no packed fp32 of its own;
   2. product build: no other kernel contains it;
   3. product build: no kernel contains v_pk_*_f32 (the victim class) except the hand-written, measured ones in PACKED_BY_HAND;
-  4. product build: no rocPRIM kernel (binning modes 1 / 2 are `make EXPERIMENTS=1`).
+  4. product build: no rocPRIM kernel (binning modes 1 / 2 are `make EXPERIMENTS=1`);
+  5. every last pass of the depth sort with the span epilogue (depth_sort_pass_kernel<3, true, ...>) takes its count-record ticket as an
+     ordered RMW: an s_waitcnt vmcnt(0) between its no-return add on the 64-bit total and the returning (sc0) ticket add, and an
+     s_waitcnt vmcnt(0) + buffer_inv between the ticket and the load of the total (depth_sort.hip: release / acquire at agent scope).
 
 usage: check_code_object.py libsgs_hip.so [product|experiments]     (exit status 1 + one line per violation)"""
 import os
@@ -27,6 +30,8 @@ OWNERS = ("blend_accum_sweep3_kernel", "bwd_fused_kernel")   # the two CU-owning
 # packed fp32 written by hand and measured: the weights pre-passes (two pixels per lane) and the SGPR-fed px4
 # fallback.  They ran beside the x16 sweep in every soak of rounds 5-6 with 0 events: what protects them is the sweep's CU ownership.
 PACKED_BY_HAND = ("blend_weights2_kernel", "blend_weights2_sb_kernel", "blend_fwd_px4_kernel", "blend_fwd_px1_kernel")
+# depth_sort_pass_kernel<PASS = 3, SPAN = true, NW, CHAIN>: the kernels that write the deferred count record (their instructions are kept)
+TICKET_KERNEL = re.compile(r"^_ZN3sgs22depth_sort_pass_kernelILi3ELb1ELi(\d+)ELb([01])E")
 
 
 def tool(name):
@@ -78,7 +83,8 @@ def kernel_metadata(elf):
 
 
 def scan(so):
-    """-> {mangled kernel name: metadata + 'packed_f32_instructions' + 'x16_instructions'} over every gfx950 code object of `so`."""
+    """-> {mangled kernel name: metadata + 'packed_f32_instructions' + 'x16_instructions'} over every gfx950 code object of `so`; the
+    kernels that match TICKET_KERNEL also get 'instructions', their body as a list of (mnemonic, operands)."""
     kernels = {}
     with tempfile.TemporaryDirectory() as td:
         for n, elf in enumerate(code_objects(so, td)):
@@ -95,8 +101,10 @@ def scan(so):
                         meta[cur].setdefault("packed_f32_instructions", 0)
                         meta[cur].setdefault("x16_instructions", 0)
                     continue
-                sp = line.split()
+                sp = line.split("//")[0].split()
                 op = sp[0] if sp else ""
+                if op and cur in meta and TICKET_KERNEL.match(cur):
+                    meta[cur].setdefault("instructions", []).append((op, " ".join(sp[1:])))
                 packed = op.startswith("v_pk_") and op.endswith("_f32")
                 x16 = op.startswith(X16)
                 if packed or x16:
@@ -110,8 +118,42 @@ def scan(so):
     return kernels
 
 
+def count_ticket_problems(insns):
+    """The ordering of the count record in one depth_sort_pass_kernel<3, true, ...> body (a list of (mnemonic, operands)): [] when the
+    ticket is ordered after this workgroup's add on the total and before the load of the total, else what is missing."""
+    ops = [o for o, _ in insns]
+    adds = [i for i, o in enumerate(ops) if o == "global_atomic_add_x2"]
+    if len(adds) != 1:
+        return [f"{len(adds)} global_atomic_add_x2 (the add on the 64-bit total), expected 1"]
+    a = adds[0]
+    tick = next((i for i in range(a + 1, len(ops)) if ops[i] == "global_atomic_add"), None)
+    if tick is None:
+        return ["no global_atomic_add (the ticket) after the add on the total"]
+    bad = []
+
+    def waits(lo, hi):
+        return any(ops[i] == "s_waitcnt" and "vmcnt(0)" in insns[i][1] for i in range(lo, hi))
+    if not waits(a + 1, tick):
+        bad.append("no s_waitcnt vmcnt(0) between the add on the total and the ticket: the add may still be in flight when the ticket is drawn")
+    if "sc0" not in insns[tick][1].split():
+        bad.append(f"the ticket is not the returning form (sc0): {insns[tick][1]}")
+    load = next((i for i in range(tick + 1, len(ops)) if ops[i] == "global_load_dwordx2"), None)
+    if load is None:
+        bad.append("no global_load_dwordx2 (the load of the total) after the ticket")
+    else:
+        inv = next((i for i in range(tick + 1, load) if ops[i] == "buffer_inv"), None)
+        if inv is None or not waits(tick + 1, inv):
+            bad.append("no s_waitcnt vmcnt(0) + buffer_inv between the ticket and the load of the total: the last workgroup may read a stale total")
+    return bad
+
+
 def violations(kernels, product):
     bad = []
+    tickets = [n for n in kernels if TICKET_KERNEL.match(n)]
+    if not tickets:
+        bad.append("no depth_sort_pass_kernel<3, true, ...> instantiation: the count-record check has lost its subject")
+    for n in sorted(tickets):
+        bad += [f"{n}: {p}" for p in count_ticket_problems(kernels[n].get("instructions", []))]
     x16 = sorted(n for n, k in kernels.items() if k["x16_instructions"])
     owners = [n for n in x16 if any(o in n for o in OWNERS)]
     if not product:   # the development instantiations (ablations, phase stamps: template argument DBG != 0) are not held to the invariant
@@ -161,7 +203,8 @@ def main(argv):
     if not bad:
         nx = sum(1 for k in ks.values() if k["x16_instructions"])
         print(f"check_code_object: {len(ks)} kernels, {nx} on the x16 MFMA (256 registers, 512 threads, own their CU), "
-              f"{sum(1 for k in ks.values() if k['packed_f32_instructions'])} with hand-written packed fp32" + ("" if product else " [experiments build: owners only]"))
+              f"{sum(1 for k in ks.values() if k['packed_f32_instructions'])} with hand-written packed fp32, "
+              f"{sum(1 for n in ks if TICKET_KERNEL.match(n))} sort passes with an ordered count ticket" + ("" if product else " [experiments build: owners only]"))
     return 1 if bad else 0
 
 

@@ -303,11 +303,14 @@ __global__ __launch_bounds__(64 * NW) void depth_sort_pass_kernel(
 			unsigned long long tot = 0;
 #pragma unroll
 			for (int w = 0; w < NW; w++) tot += s_sum[w];
-			const unsigned long long before = atomicAdd(so.total, tot);
+			atomicAdd(so.total, tot);
 			if (so.cc_done) {
-				// the count record (capi.hip count_check_kernel) by whichever workgroup is last: its ticket is taken only when its own add has
-				// RETURNED (the data dependence on `before`), so the last ticket sees every workgroup's add in the total it then reads
-				const uint32_t mine = __hip_atomic_fetch_add(so.cc_done, 1u + (uint32_t)(before & 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				// the count record (capi.hip count_check_kernel) by whichever workgroup is last.  The ticket is an agent-scope acq_rel RMW: its
+				// release half orders this workgroup's add on the total before the ticket (buffer_wbl2 + s_waitcnt vmcnt(0) in front of it), its
+				// acquire half orders, in the workgroup that draws gridDim.x - 1, every earlier ticket -- and so every other workgroup's add --
+				// before the load of the total below (s_waitcnt vmcnt(0) + buffer_inv behind it).  tests/test_code_object.py reads this in the
+				// library's code objects.
+				const uint32_t mine = __hip_atomic_fetch_add(so.cc_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
 				if (mine == gridDim.x - 1u) {
 					const unsigned long long rl = __hip_atomic_load(so.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					const unsigned long long L = rl & 0xffffffffull, R = rl >> 32;

@@ -61,15 +61,17 @@ __device__ __forceinline__ float ndc2pix(float v, int S)
 	return (float)((((double)v + 1.0) * (double)S - 1.0) * 0.5);
 }
 
-// auxiliary.h:46-56 -- fp32 arithmetic, C cast (truncation), clamp to [0, grid].
+// auxiliary.h:46-56 -- fp32 arithmetic, C cast (truncation), clamp to [0, grid].  The upper bound is p + r + BLOCK - 1 in C's
+// left-to-right order, ((p + r) + 16) - 1: two roundings, not one of (p + r) + 15 (x = 488.99997, r = 8 gives 512 there and
+// 511.99997 here: a tile more; tests/test_configs_gpu.py::test_three_level_sort_forward_and_deferred_count meets such a Gaussian).
 __device__ __forceinline__ void get_rect(float px, float py, int max_radius, int gx, int gy,
 					 uint32_t& x0, uint32_t& y0, uint32_t& x1, uint32_t& y1)
 {
 	const float r = (float)max_radius;
 	x0 = (uint32_t)imin_(gx, imax_(0, (int)((px - r) / (float)SGS_TILE)));
 	y0 = (uint32_t)imin_(gy, imax_(0, (int)((py - r) / (float)SGS_TILE)));
-	x1 = (uint32_t)imin_(gx, imax_(0, (int)((px + r + (float)(SGS_TILE - 1)) / (float)SGS_TILE)));
-	y1 = (uint32_t)imin_(gy, imax_(0, (int)((py + r + (float)(SGS_TILE - 1)) / (float)SGS_TILE)));
+	x1 = (uint32_t)imin_(gx, imax_(0, (int)((px + r + (float)SGS_TILE - 1.0f) / (float)SGS_TILE)));
+	y1 = (uint32_t)imin_(gy, imax_(0, (int)((py + r + (float)SGS_TILE - 1.0f) / (float)SGS_TILE)));
 }
 
 // wave64 sum -> valid in every lane (DPP butterflies inside rows of 16, then readlane).

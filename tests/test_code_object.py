@@ -80,3 +80,38 @@ def test_the_check_catches_a_kernel_that_lost_its_registers(kernels):
     ks[victim]["x16_instructions"] = 1
     v = cco.violations(ks, True)
     assert any("outside the two CU-owning designs" in x for x in v) and any("packed-fp32" in x for x in v)
+
+
+def test_count_record_ticket_is_ordered_after_the_total(kernels):
+    """csrc/depth_sort.hip, last pass with the span epilogue: the workgroup that draws the last cc_done ticket writes the deferred count
+    record (num_rendered, major instances, trap, abort) from the 64-bit total every workgroup adds to.  A total read before some add has
+    landed under-reports L or R with abort = 0, and the span partitions and the blend then write past buffers sized for the guess.  The
+    order has to exist in the instructions: an s_waitcnt vmcnt(0) between the no-return add on the total and the returning (sc0) ticket,
+    and an s_waitcnt vmcnt(0) + buffer_inv between the ticket and the load of the total -- in every shipped form (16 waves chained; 16, 8
+    and 4 waves unchained)."""
+    forms = {}
+    for n, k in kernels.items():
+        m = cco.TICKET_KERNEL.match(n)
+        if m:
+            forms[(int(m.group(1)), m.group(2) == "1")] = n
+    assert set(forms) == {(16, True), (16, False), (8, False), (4, False)}, sorted(forms)
+    for form, n in sorted(forms.items()):
+        insns = kernels[n]["instructions"]
+        assert sum(1 for o, _ in insns if o == "global_atomic_add_x2") == 1, form
+        assert cco.count_ticket_problems(insns) == [], form
+
+
+def test_the_ticket_check_catches_an_unordered_ticket(kernels):
+    """The check itself: the relaxed ticket (no wait between the add and the ticket, no invalidate behind it), a no-return ticket, and a
+    kernel that lost its add on the total are each reported."""
+    n = next(n for n in kernels if cco.TICKET_KERNEL.match(n))
+    insns = kernels[n]["instructions"]
+    a = next(i for i, (o, _) in enumerate(insns) if o == "global_atomic_add_x2")
+    t = next(i for i in range(a + 1, len(insns)) if insns[i][0] == "global_atomic_add")
+    fenceless = [x for i, x in enumerate(insns) if not (a < i < t and x[0] in ("s_waitcnt", "buffer_wbl2"))
+                 and not (i > t and x[0] == "buffer_inv")]
+    p = cco.count_ticket_problems(fenceless)
+    assert any("between the add on the total and the ticket" in x for x in p) and any("buffer_inv" in x for x in p), p
+    noret = [(o, ops.replace(" sc0", "")) if i == t else (o, ops) for i, (o, ops) in enumerate(insns)]
+    assert any("returning form" in x for x in cco.count_ticket_problems(noret))
+    assert any("global_atomic_add_x2" in x for x in cco.count_ticket_problems([x for x in insns if x[0] != "global_atomic_add_x2"]))

@@ -28,11 +28,11 @@ def _oracle_front(orc, scene, cam, W, H):
     return pre, orc.binning(pre, W, H)
 
 
-def _forward(s, c, feats, bg, W, H, want_depth=False, pool=None):
+def _forward(s, c, feats, bg, W, H, want_depth=False, pool=None, fn=None, **kw):
     from sgs_hip import raster
-    return raster.rasterize_forward(bg, s.means3D, feats, s.opacities, s.scales, s.rotations, 1.0, E,
-                                    c.world_view_transform, c.full_proj_transform, c.tanfovx, c.tanfovy, H, W, E, 0,
-                                    c.camera_center, False, False, feats.shape[1], want_depth, pool=pool)
+    return (fn or raster.rasterize_forward)(bg, s.means3D, feats, s.opacities, s.scales, s.rotations, 1.0, E,
+                                            c.world_view_transform, c.full_proj_transform, c.tanfovx, c.tanfovy, H, W, E, 0,
+                                            c.camera_center, False, False, feats.shape[1], want_depth, pool=pool, **kw)
 
 
 def _check_integers(raster, out, pre, binn, P, W, H):
@@ -125,6 +125,62 @@ def test_cfg4_5m_gaussians_768_channels_64bit_indexing(orc):
         ids = np.concatenate([binn["point_list"][a:b] for a, b in r])
         high += int((ids.astype(np.int64) * C >= 2 ** 31).sum())
     assert high > 1000       # the sampled rows really do gather rows beyond the 32-bit element index
+
+
+def test_three_level_sort_forward_and_deferred_count(orc):
+    """P = 9 000 001 Gaussians: 2 198 tiles of the depth sort, 69 groups -- past the 64-group switch, so the forward's sort runs its
+    three-level form (super-group rows, unchained passes) and the count record is written by the last of 2 198 workgroups of the last
+    pass.  Every integer output of the full frame against the oracle, n_contrib and the exact-arithmetic feature map on one tile row;
+    then, on a fresh stream, a blocking forward that teaches the stream its capacity guess, a deferred forward that must fit it and
+    return the same count and bits without a retry, and one whose capacity no frame fits, which must be rendered again."""
+    from sgs_hip import raster, _lib
+    from sgs_hip.synthetic import CONFIGS, make_config
+    P, C = 9_000_001, 128
+    _, _, W, H, fx = CONFIGS["cfg2_half"]                           # 648 x 484
+    assert (P + 4095) // 4096 > 64 * 32
+    scene, cam = make_config("cfg2_half", P=P, C=C, features=False)
+    g = torch.Generator(device=DEV).manual_seed(9)
+    feats = torch.randn(P, C, device=DEV, generator=g)              # features made on the device, as for cfg4
+    feats /= feats.norm(dim=1, keepdim=True)
+    bg = torch.linspace(-1.0, 1.0, C, device=DEV)
+    pre, binn = _oracle_front(orc, scene, cam, W, H)
+    s, c = scene._replace(features=torch.empty(0, C)).to(DEV), cam.to(DEV)
+    out = _forward(s, c, feats, bg, W, H)
+    iv = _check_integers(raster, out, pre, binn, P, W, H)
+    n, default = out[0], out[1]
+    raster.set_blend_exact(True)
+    try:
+        exact = _forward(s, c, feats, bg, W, H)[1]
+    finally:
+        raster.set_blend_exact(False)
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    row = gy // 2
+    ob = orc.blend_forward(pre, binn, feats.cpu().numpy(), bg.cpu().numpy(), W, H, tile_lo=row * gx, tile_hi=(row + 1) * gx)
+    rows = slice(row * 16, row * 16 + 16)
+    want = ob["out"][:, rows]
+    assert np.array_equal(exact[:, rows].cpu().numpy().view(np.uint32), want.view(np.uint32))
+    assert np.abs(default[:, rows].cpu().numpy() - want).max() <= 1e-4 * np.abs(want).max()
+    assert np.array_equal(iv["n_contrib"][rows].cpu().numpy().view(np.uint32), ob["n_contrib"][rows])
+    default = default.clone()
+    radii_want = torch.from_numpy(pre["radii"]).to(DEV)
+    del out, exact, iv
+    st = torch.cuda.Stream(DEV)                                     # a fresh stream: no capacity guess yet
+    st.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(st):
+        first = _forward(s, c, feats, bg, W, H)                     # blocking: the guess this stream's deferred frames are sized by
+        assert first[0] == n and torch.equal(first[1], default)
+        del first
+        deferred = raster.stream_stat(_lib.STAT_DEFERRED_FORWARDS)
+        h = _forward(s, c, feats, bg, W, H, fn=raster.rasterize_forward_deferred)
+        o = h.result()
+        assert raster.stream_stat(_lib.STAT_DEFERRED_FORWARDS) == deferred + 1   # the count came from the sort's count record
+        assert not h.retried and o[0] == n and torch.equal(o[1], default) and torch.equal(o[2], radii_want)
+        del o, h
+        h = _forward(s, c, feats, bg, W, H, fn=raster.rasterize_forward_deferred, _defer_mode=2)
+        o = h.result()
+        assert h.retried and o[0] == n and torch.equal(o[1], default) and torch.equal(o[2], radii_want)
+        del o, h
+        raster.release_stream()
 
 
 def test_cfg5_gaussian_sharding_two_depth_slabs(orc):

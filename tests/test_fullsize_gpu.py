@@ -24,14 +24,14 @@ def cfg3():
     return scene, pinhole(W, H, fx), (P, C, W, H)
 
 
-def _render(scene_dev, cam_dev, C, W, H, feats=None, bg=None):
+def _render(scene_dev, cam_dev, C, W, H, feats=None, bg=None, fn=None, **kw):
     from sgs_hip import raster
     e = torch.Tensor([])
     s, c = scene_dev, cam_dev
-    return raster.rasterize_forward(
+    return (fn or raster.rasterize_forward)(
         s.bg[:C] if bg is None else bg, s.means3D, s.features if feats is None else feats, s.opacities, s.scales,
         s.rotations, 1.0, e, c.world_view_transform, c.full_proj_transform, c.tanfovx, c.tanfovy, H, W, e, 0,
-        c.camera_center, False, False, C, False)
+        c.camera_center, False, False, C, False, **kw)
 
 
 def test_cfg3_lists_sorted_consistent_and_identical_across_binning_modes(cfg3, orc):
@@ -73,9 +73,9 @@ def test_cfg3_lists_sorted_consistent_and_identical_across_binning_modes(cfg3, o
     m2d, rad = g["means2D"][plist], a["radii"][plist].float()
     tx, ty = (tile_of % gx).float(), (tile_of // gx).float()
     x0 = torch.clamp(torch.floor((m2d[:, 0] - rad) / 16.0), 0, gx)
-    x1 = torch.clamp(torch.floor((m2d[:, 0] + rad + 15.0) / 16.0), 0, gx)
+    x1 = torch.clamp(torch.floor((m2d[:, 0] + rad + 16.0 - 1.0) / 16.0), 0, gx)
     y0 = torch.clamp(torch.floor((m2d[:, 1] - rad) / 16.0), 0, gy)
-    y1 = torch.clamp(torch.floor((m2d[:, 1] + rad + 15.0) / 16.0), 0, gy)
+    y1 = torch.clamp(torch.floor((m2d[:, 1] + rad + 16.0 - 1.0) / 16.0), 0, gy)
     assert bool(((tx >= x0) & (tx < x1) & (ty >= y0) & (ty < y1)).all())
     # the oracle on everything integer at full size
     pre = orc.preprocess(scene.means3D.numpy(), scene.opacities.numpy(), cam.world_view_transform.numpy(),
@@ -286,3 +286,46 @@ def test_cfg3_pipelined_views_match_serial(cfg3):
             assert torch.equal(r0, r1), (i, "radii")
             assert torch.equal(c0, c1), (i, "color")
         del piped
+
+
+def test_cfg3_deferred_count_and_the_drop_in_module_under_no_grad(cfg3):
+    """The deferred count at the headline size: 1 M Gaussians, 245 workgroups in the sort's last pass (chained form), the last of them
+    writes the count record.  On a fresh stream a blocking forward teaches the stream its capacity guess; a deferred forward must then
+    return the same num_rendered and bits without a retry, and one whose capacity no frame fits must be rendered again.  Then the drop-in
+    GaussianRasterizer under torch.no_grad() -- the path fusion.py and eval_segmentation.py take (deferred, resident inference pool) --
+    must give the tracked call's image and radii bit for bit."""
+    from sgs_hip import raster, _lib
+    import channel_rasterization as chn
+    scene, cam, (P, C, W, H) = cfg3
+    s, c = scene.to(DEV), cam.to(DEV)
+    st = torch.cuda.Stream(DEV)   # a fresh stream: no capacity guess yet
+    st.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(st):
+        n, color, radii, *_ = _render(s, c, C, W, H)
+        assert n > 10_000_000
+        h = _render(s, c, C, W, H, fn=raster.rasterize_forward_deferred)
+        o = h.result()
+        assert not h.retried and o[0] == n and torch.equal(o[1], color) and torch.equal(o[2], radii)
+        del o, h
+        h = _render(s, c, C, W, H, fn=raster.rasterize_forward_deferred, _defer_mode=2)
+        o = h.result()
+        assert h.retried and o[0] == n and torch.equal(o[1], color) and torch.equal(o[2], radii)
+        del o, h
+        settings = chn.GaussianRasterizationSettings(
+            image_height=H, image_width=W, tanfovx=c.tanfovx, tanfovy=c.tanfovy, bg=s.bg[:C], scale_modifier=1.0,
+            viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=0, campos=c.camera_center,
+            prefiltered=False, debug=False, num_channels=C)
+        rasterizer = chn.GaussianRasterizer(settings)
+        feats = torch.nn.Parameter(s.features.clone())
+        kw = dict(means3D=s.means3D, means2D=torch.zeros_like(s.means3D, requires_grad=True), opacities=s.opacities,
+                  colors_precomp=feats, scales=s.scales, rotations=s.rotations)
+        tracked, tracked_radii = rasterizer(**kw)
+        assert tracked.requires_grad and torch.equal(tracked.detach(), color) and torch.equal(tracked_radii, radii)
+        deferred = raster.stream_stat(_lib.STAT_DEFERRED_FORWARDS)
+        with torch.no_grad():
+            image, image_radii = rasterizer(**kw)
+        assert raster.stream_stat(_lib.STAT_DEFERRED_FORWARDS) == deferred + 1   # it did take the deferred path
+        assert not image.requires_grad
+        assert torch.equal(image, tracked.detach()) and torch.equal(image_radii, tracked_radii)
+        del tracked, image
+        raster.release_stream()

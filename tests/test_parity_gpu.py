@@ -796,30 +796,58 @@ def test_pipelined_views_with_deferred_counts():
         assert isinstance(o, tuple) and torch.equal(o[1], want)
 
 
+def _sort_keys(P, kind, g):
+    """Keys of one kind for the depth-sort tests (int64 holding the uint32 bit patterns)."""
+    if kind == "random":
+        return torch.randint(0, 2 ** 32, (P,), device=DEV, generator=g, dtype=torch.int64)
+    if kind == "depth":
+        return (0.2 + 60.0 * torch.rand(P, device=DEV, generator=g)).view(torch.int32).to(torch.int64)
+    if kind == "equal":
+        return torch.full((P,), 0x40490FDB, device=DEV, dtype=torch.int64)
+    if kind == "planes":
+        return torch.tensor([1.0, 1.5, 2.0, 2.0000002, 7.25], device=DEV)[
+            torch.randint(0, 5, (P,), device=DEV, generator=g)].view(torch.int32).to(torch.int64)
+    if kind.startswith("digit"):   # one random byte at that position, the other three fixed: three passes see a single bin
+        b = 8 * int(kind[5:])
+        return (0x3FA5C35A & ~(0xFF << b)) | (torch.randint(0, 256, (P,), device=DEV, generator=g, dtype=torch.int64) << b)
+    if kind == "narrow-depth":     # the floats of [1, 2): the top byte is 0x3F throughout
+        return 0x3F800000 | torch.randint(0, 1 << 23, (P,), device=DEV, generator=g, dtype=torch.int64)
+    if kind == "all-culled":
+        return torch.full((P,), 0xFFFFFFFF, device=DEV, dtype=torch.int64)
+    assert kind == "culled", kind
+    keys = (0.2 + 5.0 * torch.rand(P, device=DEV, generator=g)).view(torch.int32).to(torch.int64)
+    keys[torch.rand(P, device=DEV, generator=g) < 0.9] = 0xFFFFFFFF
+    return keys
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("P,kind", [(1, "random"), (63, "random"), (4096, "random"), (4097, "random"),
                                     (300000, "random"), (1000003, "depth"), (200000, "equal"),
-                                    (500000, "planes"), (150001, "culled"), (5000000, "depth")])
+                                    (500000, "planes"), (150001, "culled"), (5000000, "depth"),
+                                    # 32 tiles per group: one group -> two
+                                    (131072, "random"), (131072, "narrow-depth"), (131073, "random"), (131073, "depth"),
+                                    (131073, "digit0"),
+                                    # 64 groups: the longest chained walk
+                                    (8388608, "random"), (8388608, "depth"), (8388608, "narrow-depth"),
+                                    # 65 groups: three levels, 3 super-groups, the last tile holds one key
+                                    (8388609, "random"), (8388609, "depth"), (8388609, "digit1"), (8388609, "all-culled"),
+                                    # 96 -> 97 groups: three super-groups -> four
+                                    (12582912, "random"), (12582912, "culled"), (12582912, "digit2"),
+                                    (12582913, "random"), (12582913, "narrow-depth"), (12582913, "digit3"),
+                                    # BASELINE cfg5's size: 382 groups, 12 super-groups
+                                    (50000000, "random"), (50000000, "depth"), (50000000, "digit0")])
 def test_depth_sort_matches_stable_sort(P, kind):
     """csrc/depth_sort.hip (the forward's presort of the Gaussians) on bare keys against torch's stable sort:
     full-range random keys, depth-like float bit patterns, all keys equal (ties resolve by index), a handful of
-    distinct values, mostly-culled (0xFFFFFFFF) keys, sizes around the 4096-key tile and one beyond 32 x 32 tiles."""
+    distinct values, mostly-culled (0xFFFFFFFF) and all-culled keys, keys in which a single byte varies (the other
+    passes see one bin) or the top byte is constant (floats of [1, 2)); sizes around the 4096-key tile, the 32-tile
+    group, the 64-group switch from the chained passes to three levels of count rows, a 32-group super-group, and
+    BASELINE config 5's 50 M keys."""
     import ctypes as C
     from sgs_hip import _lib
     lib = _lib.load()
     g = torch.Generator(device=DEV).manual_seed(P)
-    if kind == "random":
-        keys = torch.randint(0, 2 ** 32, (P,), device=DEV, generator=g, dtype=torch.int64)
-    elif kind == "depth":
-        keys = (0.2 + 60.0 * torch.rand(P, device=DEV, generator=g)).view(torch.int32).to(torch.int64)
-    elif kind == "equal":
-        keys = torch.full((P,), 0x40490FDB, device=DEV, dtype=torch.int64)
-    elif kind == "planes":
-        keys = torch.tensor([1.0, 1.5, 2.0, 2.0000002, 7.25], device=DEV)[
-            torch.randint(0, 5, (P,), device=DEV, generator=g)].view(torch.int32).to(torch.int64)
-    else:
-        keys = (0.2 + 5.0 * torch.rand(P, device=DEV, generator=g)).view(torch.int32).to(torch.int64)
-        keys[torch.rand(P, device=DEV, generator=g) < 0.9] = 0xFFFFFFFF
+    keys = _sort_keys(P, kind, g)
     want = torch.sort(keys, stable=True).indices.to(torch.int32)
     k32 = (keys & 0xFFFFFFFF).to(torch.int64)
     k32 = torch.where(k32 >= 2 ** 31, k32 - 2 ** 32, k32).to(torch.int32)   # same bits as uint32

@@ -103,14 +103,16 @@ def test_partitioned_forward_feeds_the_backward(orc):
 def test_chained_sort_passes_on_a_few_compute_units(cus, kind):
     """Round 6: the depth sort's passes 1 .. 3 wait, inside the kernel, for the count rows of the tiles in front of theirs (csrc/depth_sort.hip CHAIN).
     A workgroup takes its tile from a ticket, so what it waits for always belongs to a workgroup that is already running -- also when only a handful
-    of the 245 (1 M keys) / 733 (3 M keys) workgroups are resident at a time: here the sort runs on a stream confined to 4 / 32 compute units."""
+    of the 245 (1 M keys) / 733 (3 M keys) workgroups are resident at a time: here the sort runs on a stream confined to 4 / 32 compute units.
+    On 4 units also the longest chain (8 388 608 keys: 64 groups, 2 048 ticketed workgroups per pass) and, one key more, the three-level form
+    that takes over past 64 groups."""
     import ctypes as C
     from sgs_hip import _lib
     lib = _lib.load()
     st = C.c_void_p()
     assert lib.sgs_stream_create_cu_range(0, cus, C.byref(st)) == 0
     try:
-        for P in (1_000_000, 3_000_001):
+        for P in (1_000_000, 3_000_001) + ((8_388_608, 8_388_609) if cus == 4 else ()):
             g = torch.Generator(device=DEV).manual_seed(P + cus)
             if kind == "random":
                 keys = torch.randint(0, 2 ** 32, (P,), device=DEV, generator=g, dtype=torch.int64)
