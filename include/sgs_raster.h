@@ -275,7 +275,22 @@ int sgs_debug_expf(int n, const float *in, float *out, void *stream);
  * contiguous message -- no staging copy per peer.  Needs num_channels % 128 == 0, no depth plane, no SGS_OPT_NORM_PLANE and the default /
  * ping-pong sweep (variants 0, 6, word nibbles 4 / 6); SGS_EINVAL otherwise. */
 #define SGS_OPT_OUT_BANDS 8
-#define SGS_OPT_COUNT 9
+/* Element type of colors_precomp for the NEXT forward on this stream (ONE call, like SGS_OPT_OUT_PITCH; consumed before the forward's first
+ * early return): 0 (default) = fp32; 1 = fp16 -- colors_precomp is then (P, C) row-major _Float16 (pass it through the `const float *`
+ * parameter).  Each value is converted to fp32 exactly where it is loaded; bg, the arithmetic and out_color are unchanged, and the table
+ * holds half the device memory (1M x 512: 1 GB instead of 2).  Bit-identity with the fp32 render of the same table converted to fp32 (map,
+ * final_T, n_contrib, radii):
+ *   - under the same variant -- 0 (the ping-pong sweep and its x8 fallback, the gated fallback, the remainder channels, SGS_OPT_OUT_BANDS), 6 and
+ *     15 (rendered by the px4 form, the contract's fp32 chain, which 15 reproduces) -- when C < 128 or C % 8 == 0 and colors_precomp is 16-byte
+ *     aligned (torch allocations are);
+ *   - otherwise (C >= 128, C % 8 != 0, or an unaligned table: the fp16 rows do not fit the sweep's 16-byte LDS-DMA pieces) variants 0 and 6 render
+ *     fp16 on the px4 form, bit-identical to the fp32 table under variant 6 (not to the fp32 default's split-bf16 sweep) and about twice the
+ *     sweep's time.
+ * With SGS_OPT_NORM_PLANE the px4 form's norm epilogue renders the plane.  SGS_EINVAL for fp16 with SH input (no colors_precomp), with a depth
+ * plane (the RGB-D variant), with variant 14 or any development word; any value other than 0 / 1 is refused when it is set (2 is kept for
+ * bf16).  sgs_rasterize_backward reads fp32 colours only. */
+#define SGS_OPT_FEATURE_FORMAT 9
+#define SGS_OPT_COUNT 10
 /* value < 0 removes the override (the stream follows the process default again).  Returns the previous override,
  * or 0x7fffffff if there was none. */
 int sgs_stream_set_option(void *stream, int option, int value);

@@ -503,13 +503,14 @@ bool blend_forward_fused_pc_eligible(const BlendFwdArgs& a)
 
 hipError_t launch_blend_forward_fused_pc(hipStream_t st, const BlendFwdArgs& a, bool exact, int seg_tiles, int dbg)
 {
+	if (a.fmt != 0) return hipErrorInvalidValue;   // (fp32 feature rows only)
 	static bool attr_set[2] = {false, false};
 	FusedArgs f;
 	f.ranges = a.ranges;
 	f.point_list = a.point_list;
 	f.means2D = a.means2D;
 	f.conic_opacity = a.conic_opacity;
-	f.features = a.features;
+	f.features = a.features_f32();
 	f.bg = a.bg;
 	f.out = a.out;
 	f.final_T = a.final_T;

@@ -34,6 +34,13 @@ namespace sgs {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
+// Feature elements (SGS_OPT_FEATURE_FORMAT): fp32, or fp16 converted on load -- exactly, so an fp16 table renders bit-identically to
+// its fp32 upcast.  fp16 rows are only 2-byte aligned for odd C, so they are read element by element (no paired scalar load).
+__device__ __forceinline__ float feat_at(const float* __restrict__ f, int c) { return f[c]; }
+__device__ __forceinline__ float feat_at(const _Float16* __restrict__ f, int c) { return (float)f[c]; }
+__device__ __forceinline__ f2 feat_pair(const float* __restrict__ f, int c) { return reinterpret_cast<const f2*>(f)[c]; }
+__device__ __forceinline__ f2 feat_pair(const _Float16* __restrict__ f, int c) { return f2{(float)f[2 * c], (float)f[2 * c + 1]}; }
+
 struct StagedEntry {   // 32 B per list entry in LDS
 	float a2, b2, c2, o;   // -0.5*conic.x, -conic.y, -0.5*conic.z, opacity
 	float x, y;            // pixel centre
@@ -82,10 +89,10 @@ __device__ __forceinline__ bool eval_pixel(const StagedEntry& e, float pxf, floa
 // px1: lane = pixel, CC channels per workgroup.
 //   FULL : every chunk has exactly CC channels (no per-channel bounds checks)
 //   XCD  : XCD-aware block map (grid is padded to 8*per_xcd)
-template <int CC, bool DEPTH, bool FULL>
+template <int CC, bool DEPTH, bool FULL, typename FT = float>
 __global__ __launch_bounds__(256) void blend_fwd_px1_kernel(
 	const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
-	const float2* __restrict__ means2D, const float* __restrict__ features,
+	const float2* __restrict__ means2D, const FT* __restrict__ features,
 	const float4* __restrict__ conic_opacity, const float* __restrict__ depths,
 	const float* __restrict__ bg, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
 	float* __restrict__ out, float* __restrict__ out_depth, int W, int H, int C, int gx,
@@ -142,10 +149,10 @@ __global__ __launch_bounds__(256) void blend_fwd_px1_kernel(
 				if (__ballot(take) != 0ull) {
 					const float w = take ? alpha * T : 0.0f;
 					const uint32_t id = __builtin_amdgcn_readfirstlane(e.id);
-					const float* __restrict__ f = features + (size_t)id * C + c0;
+					const FT* __restrict__ f = features + (size_t)id * C + c0;
 #pragma unroll
 					for (int c = 0; c < CC; c++)
-						if (FULL || c < cn) acc[c] = __builtin_fmaf(f[c], w, acc[c]);
+						if (FULL || c < cn) acc[c] = __builtin_fmaf(feat_at(f, c), w, acc[c]);
 					if (DEPTH) {
 						if (take && T > 0.5f && test_T < 0.5f) D = e.depth;
 					}
@@ -178,10 +185,10 @@ __global__ __launch_bounds__(256) void blend_fwd_px1_kernel(
 // LDS per workgroup: BATCH staged entries (32 B each) + BATCH x 256 weights (4 B each),
 // weight layout [entry][lane][strip] so that lane l reads its four pixels
 // (strip 0..3, position l) with one ds_read_b128.
-template <int CW, int BATCH>
+template <int CW, int BATCH, typename FT = float>
 __global__ __launch_bounds__(256) void blend_fwd_px4_kernel(
 	const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
-	const float2* __restrict__ means2D, const float* __restrict__ features,
+	const float2* __restrict__ means2D, const FT* __restrict__ features,
 	const float4* __restrict__ conic_opacity, const float* __restrict__ bg,
 	float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out, int W,
 	int H, int C, int gx, int nchunks, int per_xcd, int total, const uint32_t* __restrict__ gate, int pitch,
@@ -260,11 +267,11 @@ __global__ __launch_bounds__(256) void blend_fwd_px4_kernel(
 			if (s_active[j] == 0u) continue;
 			const float4 w4 = s_w[j * 64 + lane];
 			const uint32_t id = __builtin_amdgcn_readfirstlane(s_e[j].id);
-			const f2* __restrict__ f = reinterpret_cast<const f2*>(features + (size_t)id * C + c0);
+			const FT* __restrict__ f = features + (size_t)id * C + c0;
 			const f2 w0 = {w4.x, w4.x}, w1 = {w4.y, w4.y}, w2 = {w4.z, w4.z}, w3 = {w4.w, w4.w};
 #pragma unroll
 			for (int c = 0; c < CW / 2; c++) {
-				const f2 fv = f[c];
+				const f2 fv = feat_pair(f, c);
 				acc[0][c] = __builtin_elementwise_fma(fv, w0, acc[0][c]);
 				acc[1][c] = __builtin_elementwise_fma(fv, w1, acc[1][c]);
 				acc[2][c] = __builtin_elementwise_fma(fv, w2, acc[2][c]);
@@ -330,10 +337,19 @@ static void launch_px1(hipStream_t st, const BlendFwdArgs& a, int c_begin, int n
 {
 	const int total = a.gx * a.gy * nchunks;
 	const int per_xcd = (total + 7) / 8;
-	hipLaunchKernelGGL((blend_fwd_px1_kernel<CC, DEPTH, FULL>), dim3(per_xcd * 8), dim3(256), 0, st,
-			   a.ranges, a.point_list, a.means2D, a.features, a.conic_opacity, a.depths,
-			   a.bg, a.final_T, a.n_contrib, a.out, a.out_depth, a.W, a.H, a.C, a.gx, c_begin,
-			   nchunks, write_aux, per_xcd, total, a.pitch, a.abort);
+#define PX1_LAUNCH(FT_)                                                                              \
+	hipLaunchKernelGGL((blend_fwd_px1_kernel<CC, DEPTH, FULL, FT_>), dim3(per_xcd * 8), dim3(256), 0, st, \
+			   a.ranges, a.point_list, a.means2D, static_cast<const FT_*>(a.features), a.conic_opacity, a.depths, \
+			   a.bg, a.final_T, a.n_contrib, a.out, a.out_depth, a.W, a.H, a.C, a.gx, c_begin,   \
+			   nchunks, write_aux, per_xcd, total, a.pitch, a.abort)
+	if constexpr (!DEPTH) {   // (fp16 tables: not with the RGB-D variant's depth plane, capi.hip refuses that)
+		if (a.fmt == 1) {
+			PX1_LAUNCH(_Float16);
+			return;
+		}
+	}
+	PX1_LAUNCH(float);
+#undef PX1_LAUNCH
 }
 
 // workgroups of the GATED instance (it exits at once unless the split path's work list overflowed): every one of them
@@ -347,9 +363,13 @@ static void launch_px4(hipStream_t st, const BlendFwdArgs& a, int nchunks, const
 	const int total = a.gx * a.gy * nchunks;
 	const int per_xcd = (total + 7) / 8;
 	const int grid = gate && per_xcd * 8 > SGS_GATED_GRID ? SGS_GATED_GRID : per_xcd * 8;   // (gated fallback: see the kernel)
-	hipLaunchKernelGGL((blend_fwd_px4_kernel<CW, BATCH>), dim3(grid), dim3(256), 0, st,
-			   a.ranges, a.point_list, a.means2D, a.features, a.conic_opacity, a.bg,
-			   a.final_T, a.n_contrib, a.out, a.W, a.H, a.C, a.gx, nchunks, per_xcd, total, gate, a.pitch, a.abort, a.norm_plane ? 1 : 0, a.bands);
+#define PX4_LAUNCH(FT_)                                                                              \
+	hipLaunchKernelGGL((blend_fwd_px4_kernel<CW, BATCH, FT_>), dim3(grid), dim3(256), 0, st,           \
+			   a.ranges, a.point_list, a.means2D, static_cast<const FT_*>(a.features), a.conic_opacity, a.bg, \
+			   a.final_T, a.n_contrib, a.out, a.W, a.H, a.C, a.gx, nchunks, per_xcd, total, gate, a.pitch, a.abort, a.norm_plane ? 1 : 0, a.bands)
+	if (a.fmt == 1) PX4_LAUNCH(_Float16);
+	else PX4_LAUNCH(float);
+#undef PX4_LAUNCH
 }
 
 // variant: 0 = default (px4 CW=32 for the 128-channel-aligned part, px1 for the rest)
@@ -361,6 +381,7 @@ hipError_t launch_blend_forward(hipStream_t st, const BlendFwdArgs& a, int varia
 	const int ntiles = a.gx * a.gy;
 	if (ntiles == 0 || a.C == 0) return hipSuccess;
 	const bool depth = a.out_depth != nullptr;
+	if (a.fmt != 0 && (depth || a.fmt != 1)) return hipErrorInvalidValue;   // fp16 tables: N-channel maps only
 	int c_done = 0;
 	if (c_skip > 0 && !gate) {
 		c_done = c_skip;   // channels [0, c_skip) were rendered by the split path

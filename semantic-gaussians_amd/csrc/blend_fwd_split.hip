@@ -1502,8 +1502,9 @@ hipError_t launch_blend_forward_split(hipStream_t st, const BlendFwdArgs& a, cha
 		const uint32_t* order_arg = plan == 3 ? order : nullptr;
 #define SGS_LAUNCH_SWEEP(D_, E_)                                                                     \
 	hipLaunchKernelGGL((blend_accum_sweep_kernel<D_, E_>), dim3(pxcd * 8), dim3(256), 0, st, a.ranges, table, \
-			   nbatches, act_id, (const char*)wgt, a.features, a.bg, a.out, counter, a.W,   \
+			   nbatches, act_id, (const char*)wgt, a.features_f32(), a.bg, a.out, counter, a.W,   \
 			   a.H, a.C, a.gx, nc, seg, nseg, pxcd, items, a.pitch, g_sweep_trace, order_arg, dealt)
+		if (a.fmt != 0 && !sweep3) return hipErrorInvalidValue;   // fp16 tables: the ping-pong sweep only (capi.hip routes the rest to px4)
 		if (sweep3) {
 			const hipError_t e3 = launch_accum_sweep3(st, (split_mode >> 8) & 15, a, table, nbatches, act_id, (const char*)wgt, counter,
 								  nc, seg, nseg, pxcd, items, g_sweep_trace, order_arg, dealt, (split_mode >> 16) & 15, sweep3c ? 1 : (sweep3f ? 2 : 0), (split_mode >> 20) & 3);

@@ -1151,11 +1151,17 @@ constexpr int S3_STAGE_OF(bool coop) { return 8192 + 2 * S3_WB(coop) + 8 * 256; 
 // bit-identical maps).  Sweep 1.017 -> 0.983 ms, order-balanced over three boxes (profiles/r06_sweep_store_placement*.txt).  Two more placements were built
 // on this hook, measured and removed: the four deferred chunks in that matrix-phase slot as well (no store in a PREP phase at all): +2 %; the chunks behind
 // the step's LAST products, in front of the arrival check's wait: +10 % (1.10 ms) -- stores at the end of a matrix phase delay the wave's own DMA pieces' arrival check.
-template <int DBG, int MM = 0, bool COOP = false, bool FREE = false, int STP = 0>
+// FMT (SGS_OPT_FEATURE_FORMAT; product forms only: the default and the x8 lock-step fallback): 0 = fp32 feature rows; 1 = fp16 rows.  An fp16
+// row of the chunk is 256 B = 16 lanes x 16 B, so four waves (channel groups 0, 1 of both halves) DMA four rows each and the other four issue
+// no feature piece; the stage keeps its size (the rows fill its first 4 KB).  The operand phase reads the lane's eight 2-byte values and
+// converts them (exact) before the split, whose third term is then zero.  The closing T * bg entry keeps bg's full fp32 value: the lane's
+// bg[c] is loaded once and replaces the entries from the tile's last one on (those are bg rows in the fp32 form too, ids clamped to it) --
+// so an fp16 table renders BIT-IDENTICALLY to its fp32 upcast (same products, same order, same accumulators).
+template <int DBG, int MM = 0, bool COOP = false, bool FREE = false, int STP = 0, int FMT = 0>
 __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 	const uint2* __restrict__ ranges, const uint32_t* __restrict__ table,
 	const uint32_t* __restrict__ nact, const uint32_t* __restrict__ act_id,
-	const char* __restrict__ wgt, const float* __restrict__ features,
+	const char* __restrict__ wgt, const void* __restrict__ features_v,
 	const float* __restrict__ bg, float* __restrict__ out_img, const uint32_t* __restrict__ counter,
 	int W, int H_img, int C, int gx, int nchunks_c, int seg, int nseg, int per_xcd, int total_items, int PW,
 	unsigned long long* __restrict__ trace, const uint32_t* __restrict__ order, int dealt, int tune, int bands)
@@ -1209,6 +1215,12 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 	const int cbase = chunk * 128;
 	const int c0 = cbase + cg * 32;
 	const size_t HW = (size_t)H * PW;
+	static_assert(FMT == 0 || (FMT == 1 && !COOP && DBG == 0), "fp16 feature rows: product forms only");
+	const float* __restrict__ features = static_cast<const float*>(features_v);
+	const _Float16* __restrict__ features_h = static_cast<const _Float16*>(features_v);
+	const float bg_lane = FMT ? bg[c0 + l31] : 0.f;   // (FMT 1) this lane's channel of the closing entry, at full precision
+	const int fwave = (wave & 1) + 2 * (wave >> 2);   // (FMT 1) index of the feature-fetching wave (wave & 2 == 0), rows 4 fwave .. 4 fwave + 3
+	const bool fetch_rows = FMT == 0 || (wave & 2) == 0;   // (uniform)
 
 	constexpr int S3_STAGE = S3_STAGE_OF(COOP), WB = S3_WB(COOP);
 	constexpr int NP = COOP ? 4 : 5;   // DMA pieces per wave and bundle: features | 3 pre-split / 2 fp32 weight pieces | ids
@@ -1263,7 +1275,8 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 
 	const uint32_t ring = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)s_ring;
 	const uint32_t bt_a = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)s_bt;
-	const uint32_t sub = (uint32_t)(2 * wave + half);   // this lane fetches the feature row of entry sub (one 1-KB piece = two rows per wave)
+	// this lane fetches the feature row of entry sub (fp32: one 1-KB piece = two rows per wave; fp16: four rows per fetching wave)
+	const uint32_t sub = FMT ? (uint32_t)(4 * fwave + (lane >> 4)) : (uint32_t)(2 * wave + half);
 	const uint32_t my_ids = 8192u + 2u * (uint32_t)WB + (uint32_t)wave * 256u;   // this wave's id words inside a stage
 	const uint32_t split_a = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)s_split + (uint32_t)g * 2u * 12288u;   // this parity's two split buffers
 	// bundle = features + both parities' weights of the batch at `slot` into stage st, then the ids of the batch
@@ -1280,7 +1293,10 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 	const uint32_t lane16 = COOP ? (uint32_t)(lane >> 3) * 1024u + (uint32_t)(lane & 7) * 16u : (uint32_t)lane * 16u;
 	auto dma_src = [&](auto I, const Bundle& bd) __attribute__((always_inline)) -> const char* {
 		constexpr int i = decltype(I)::value;
-		if constexpr (i == 0) {
+		if constexpr (i == 0 && FMT == 1) {   // (the bg entry fetches 256 B of bg, in bounds, that the operand phase replaces)
+			const char* row = bd.id0 == SGS_BG_ID ? (const char*)(bg + cbase) : (const char*)(features_h + (size_t)bd.id0 * C + cbase);
+			return row + (lane & 15) * 16;
+		} else if constexpr (i == 0) {
 			const float* row = bd.id0 == SGS_BG_ID ? bg : features + (size_t)bd.id0 * C;
 			return (const char*)(row + cbase + l31 * 4);
 		} else if constexpr (i == NP - 1) {
@@ -1296,7 +1312,11 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 	};
 	auto dma_go = [&](auto I, const char* src, uint32_t st, uint32_t voff) __attribute__((always_inline)) {
 		constexpr int i = decltype(I)::value;
-		if constexpr (i == 0)
+		if constexpr (i == 0 && FMT == 1) {
+			if (fetch_rows)
+				__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+								 (__attribute__((address_space(3))) void*)(size_t)(st + (uint32_t)fwave * 1024u), 16, 0, 0);
+		} else if constexpr (i == 0)
 			__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
 							 (__attribute__((address_space(3))) void*)(size_t)(st + (uint32_t)(2 * wave) * 512u), 16, 0, 0);
 		else {
@@ -1515,6 +1535,22 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 		if constexpr ((c_) == 3 && NP == 5) dma_go(std::integral_constant<int, 3>{}, da3_, dst_, lane16); \
 		if constexpr ((c_) == NP - 1) dma_go(std::integral_constant<int, NP - 1>{}, da4_, dst_, io4_); \
 	} while (0)
+// (FMT 1) the lane's eight fp16 values (entries 8 half .. 8 half + 7, 256 B apart), converted on the way in (exact).  Issued behind the
+// weight reads; the compiler waits for them itself (s_waitcnt lgkmcnt(0), which also covers the weight reads) ahead of the conversions, so the
+// asm lgkmcnt(6) that follows is a no-op in this form.  The entries from the tile's closing one on (last batch of a tile: entry n - 1 = T * bg, the ids behind it are clamped to it) take the lane's fp32 bg[c]
+#define S3_READ8_F16(dst)                                                                            \
+	do {                                                                                             \
+		const __attribute__((address_space(3))) _Float16* fh_ =                                      \
+			(const __attribute__((address_space(3))) _Float16*)(size_t)(st0 + (uint32_t)(8 * half * 256 + (cg * 32 + l31) * 2)); \
+		_Pragma("unroll") for (int k_ = 0; k_ < 8; k_++) dst[k_] = (float)fh_[k_ * 128];             \
+	} while (0)
+#define S3_BG_F16(dst)                                                                               \
+	do {                                                                                             \
+		if ((e_ >> 16) & 1u) {   /* (uniform) */                                                     \
+			const int nl_ = (int)(e_ & 255u) - 1 - 8 * half;                                         \
+			_Pragma("unroll") for (int k_ = 0; k_ < 8; k_++) dst[k_] = k_ >= nl_ ? bg_lane : dst[k_]; \
+		}                                                                                            \
+	} while (0)
 // One step = batch j into accumulator blocks b0_..b3_.  PREP: table words; operand reads of batch j go out first (stage j
 // landed before the barrier this phase began with); the DMA pieces of bundle j + LA and the deferred stores (DEF_) are
 // issued while they land; the feature split; [second half: arrival check of bundle j + 1]; barrier; MFMA: 48 products;
@@ -1553,13 +1589,15 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 		if constexpr (COOP && !(DBG & 2))   /* batch j + 1's weights (this wave's own pieces, checked a step ago) -> the other split buffer */ \
 			s2_split_coop(st1_ + (uint32_t)g * 8192u, split_a + ((j + 1u) & 1u) * 12288u, cg, half, l31); \
 		if (!(DBG & 2)) {                                                                            \
-			S2_READ8(f_, fa_);                                                                       \
+			if constexpr (FMT == 0) S2_READ8(f_, fa_);                                               \
 			S3_RDB(x_, 0);                                                                           \
 			S3_RDB(y_, (STP ? 2 : 1));   /* (STP: the dense statement takes pixel blocks 0 and 2) */  \
+			if constexpr (FMT == 1) S3_READ8_F16(f_);   /* (behind the weight reads, see S3_READ8_F16) */ \
 		}                                                                                            \
 		if (!(DBG & 2)) {                                                                            \
 			asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f_[0]), "+v"(f_[1]), "+v"(f_[2]), "+v"(f_[3]), "+v"(f_[4]), "+v"(f_[5]), "+v"(f_[6]), "+v"(f_[7]) : : "memory"); \
 			__builtin_amdgcn_sched_barrier(0);                                                       \
+			if constexpr (FMT == 1) S3_BG_F16(f_);                                                   \
 			split8(f_, A_);                                                                          \
 			S3_RDB(x2_, (STP ? 1 : 2));                                                              \
 			S3_RDB(y2_, 3);                                                                          \
@@ -1719,6 +1757,8 @@ __global__ __launch_bounds__(512, 2) void blend_accum_sweep3_kernel(
 #undef S3_PART_B
 #undef S3_PAIR_DONE
 #undef S3_RDB
+#undef S3_READ8_F16
+#undef S3_BG_F16
 }
 
 __global__ void norm_plane_background_kernel(float* __restrict__ plane, size_t n, const float* __restrict__ bg, int C)
@@ -1753,10 +1793,11 @@ bool x16_kernel_owns_cu(const void* fn, const char* name)
 	return ok;
 }
 
-int sweep3_x16_ownership()   // 1: both x16 ping-pong sweeps own their CU; 0: they do not (the x8 form runs instead)
+int sweep3_x16_ownership()   // 1: every x16 ping-pong sweep owns its CU; 0: they do not (the x8 form runs instead)
 {
 	static const int own = (x16_kernel_owns_cu((const void*)&blend_accum_sweep3_kernel<0, 1, false, true>, "blend_accum_sweep3_kernel<0, 1, false, true>") &&
 				x16_kernel_owns_cu((const void*)&blend_accum_sweep3_kernel<0, 1, false, true, 1>, "blend_accum_sweep3_kernel<0, 1, false, true, 1>") &&
+				x16_kernel_owns_cu((const void*)&blend_accum_sweep3_kernel<0, 1, false, true, 1, 1>, "blend_accum_sweep3_kernel<0, 1, false, true, 1, 1>") &&
 				x16_kernel_owns_cu((const void*)&blend_accum_sweep3_kernel<0, 1>, "blend_accum_sweep3_kernel<0, 1>")) ? 1 : 0;
 	return own;
 }
@@ -1772,6 +1813,23 @@ hipError_t launch_accum_sweep3(hipStream_t st, int dbg, const BlendFwdArgs& a, c
 		stp = 0;
 	}
 	if (stp != 0 && !(tune == 1 && form == 2)) return hipErrorInvalidValue;   // (the store placements exist for the default form only)
+	if (a.fmt == 1) {
+		// fp16 feature rows (SGS_OPT_FEATURE_FORMAT) exist in two forms: the default (free-running halves on x16, store placement 1) and the
+		// x8 lock-step form it falls back to.  Every other ping-pong word of the product library computes the same sums in the same order
+		// (bit-identical maps), so the x16 words run the default's fp16 form and the x8 ones the fallback's.
+		if (dbg != 0 || form == 1) return hipErrorInvalidValue;
+		if (tune == 1)
+			hipLaunchKernelGGL((blend_accum_sweep3_kernel<0, 1, false, true, 1, 1>), dim3(pxcd * 8), dim3(512), 0, st, a.ranges, table,
+					   nbatches, act_id, wgt, a.features, a.bg, a.out, counter, a.W, a.H, a.C, a.gx, nc, seg, nseg,
+					   pxcd, items, a.pitch, trace, order, dealt, tune, a.bands);
+		else if (tune == 0)
+			hipLaunchKernelGGL((blend_accum_sweep3_kernel<0, 0, false, false, 0, 1>), dim3(pxcd * 8), dim3(512), 0, st, a.ranges, table,
+					   nbatches, act_id, wgt, a.features, a.bg, a.out, counter, a.W, a.H, a.C, a.gx, nc, seg, nseg,
+					   pxcd, items, a.pitch, trace, order, dealt, tune, a.bands);
+		else
+			return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
 	const bool coop = form == 1;   // (form: 0 = lock step, 1 = fp32 hand-over, 2 = free-running halves)
 #define S3_LAUNCH(D_)                                                                                \
 	hipLaunchKernelGGL((blend_accum_sweep3_kernel<D_>), dim3(pxcd * 8), dim3(512), 0, st, a.ranges, table, \
@@ -1884,8 +1942,9 @@ hipError_t launch_accum_sweep2(hipStream_t st, int arith, int dbg, const BlendFw
 	static const int dyn_lds = getenv("SGS_DEBUG_SWEEP_DYNLDS") ? atoi(getenv("SGS_DEBUG_SWEEP_DYNLDS")) : 0;
 #define S2_LAUNCH(A_, D_)                                                                            \
 	hipLaunchKernelGGL((blend_accum_sweep2_kernel<A_, D_>), dim3(pxcd * 8), dim3(256), dyn_lds, st, a.ranges, table, \
-			   nbatches, act_id, wgt, a.features, a.bg, a.out, counter, a.W, a.H, a.C, a.gx, nc, seg, nseg, \
+			   nbatches, act_id, wgt, a.features_f32(), a.bg, a.out, counter, a.W, a.H, a.C, a.gx, nc, seg, nseg, \
 			   pxcd, items, a.pitch, trace, order, dealt)
+	if (a.fmt != 0) return hipErrorInvalidValue;   // (fp16 tables: capi.hip sends them to the ping-pong sweep or to px4)
 #ifndef SGS_WITH_EXPERIMENTS   // the product library: the exact fp32 sweep (variant 15) and the norm-plane epilogues of N1; the rest is make EXPERIMENTS=1
 	if (arith == S2_EXACT && dbg == 0) S2_LAUNCH(S2_EXACT, 0);
 	else if (arith == S2_EXACT && dbg == 32) S2_LAUNCH(S2_EXACT, 32);

@@ -424,6 +424,8 @@ int sgs_build_flags(void)
 int sgs_stream_set_option(void* stream, int option, int value)
 {
 	if (option < 0 || option >= SGS_OPT_COUNT) return fail(SGS_EINVAL, "unknown option");
+	if (option == SGS_OPT_FEATURE_FORMAT && value > 1)
+		return fail(SGS_EINVAL, "SGS_OPT_FEATURE_FORMAT: 0 = fp32, 1 = fp16 (no other feature format is implemented)");
 	const std::shared_ptr<StreamCtx> c = ctx_of(stream);
 	std::lock_guard<std::mutex> lk(c->mu);
 	const int prev = c->opt[option];
@@ -610,6 +612,8 @@ int sgs_rasterize_forward(sgs_alloc_fn geometry_buffer, void* geometry_user,
 	cx->opt[SGS_OPT_NORM_PLANE] = -1;
 	const int out_bands = cx->opt[SGS_OPT_OUT_BANDS];   // (one shot, stream only: there is no process default for it)
 	cx->opt[SGS_OPT_OUT_BANDS] = -1;
+	const bool feat_f16 = cx->opt[SGS_OPT_FEATURE_FORMAT] == 1;   // colors_precomp holds _Float16 (one shot, stream only)
+	cx->opt[SGS_OPT_FEATURE_FORMAT] = -1;
 	if (P < 0 || width <= 0 || height <= 0 || num_channels <= 0)
 		return fail(SGS_EINVAL, "bad sizes");
 	if (!geometry_buffer || !binning_buffer || !image_buffer || !out_color)
@@ -618,6 +622,20 @@ int sgs_rasterize_forward(sgs_alloc_fn geometry_buffer, void* geometry_user,
 		return fail(SGS_EINVAL, "For non-RGB, provide precomputed Gaussian colors!");
 	if (out_depth && num_channels != 3)
 		return fail(SGS_EINVAL, "the RGB-D variant renders exactly 3 channels");
+	if (feat_f16 && !colors_precomp)
+		return fail(SGS_EINVAL, "SGS_OPT_FEATURE_FORMAT = 1 (fp16 features) needs colors_precomp: SH input is fp32 only");
+	if (feat_f16 && out_depth)
+		return fail(SGS_EINVAL, "SGS_OPT_FEATURE_FORMAT = 1 (fp16 features) is not available with a depth plane (the RGB-D variant)");
+	const int variant = cx->option(SGS_OPT_BLEND_VARIANT);
+	// fp16 feature rows: the default's paths (the ping-pong sweep when C % 8 == 0, px4 / px1 for the gated fallback, the remainder channels and
+	// C % 8 != 0), variant 6 and variant 15 (both rendered by the px4 form: the contract's fp32 fma chain,
+	// which 15 reproduces bit for bit), the norm plane through px4's epilogue; every other variant and development word has no fp16 form.
+	// (Decided here, with the other argument checks: before any work is enqueued.)
+	const int sweep_nib = variant >= 16 ? (variant & 15) : -1;
+	if (feat_f16 && !(variant == 0 || variant == 6 || variant == 15 || ((sweep_nib == 4 || sweep_nib == 6) && ((variant >> 8) & 15) == 0)))
+		return fail(SGS_EINVAL, "SGS_OPT_FEATURE_FORMAT = 1 (fp16 features): this blend variant has no fp16 form (variants 0, 6, 15 and the ping-pong sweep words only)");
+	if (feat_f16 && norm_plane && variant == 6)
+		return fail(SGS_EINVAL, "SGS_OPT_NORM_PLANE needs the default blend (variants 0 / 15)");
 	if (P == 0) return 0;   // caller returns zeros (rasterize_points.cu:85-120)
 	if (!means3D || !opacities || !viewmatrix || !projmatrix || !background)
 		return fail(SGS_EINVAL, "null required input");
@@ -794,8 +812,7 @@ int sgs_rasterize_forward(sgs_alloc_fn geometry_buffer, void* geometry_user,
 	tm.mark();
 
 	const int sort_bits = 32 + (int)higher_msb((uint32_t)ntiles);
-	// split blend (weights pre-pass + streaming accumulate) for the 128-channel-aligned part
-	const int variant = cx->option(SGS_OPT_BLEND_VARIANT);
+	// split blend (weights pre-pass + streaming accumulate) for the 128-channel-aligned part (`variant`: read with the argument checks)
 	// variants 32 / 33: the fused single-kernel blend (split-bf16 / exact fp32), bits [11:8] = segment length / 2
 	// 32-35: the experimental single-kernel blends (contiguous output only)
 #ifdef SGS_WITH_FUSED   // (make FUSED=1: the two single-kernel experiments of round 2, DESIGN.md 5.6 -- evidence, not product)
@@ -828,7 +845,10 @@ int sgs_rasterize_forward(sgs_alloc_fn geometry_buffer, void* geometry_user,
 			return fail(SGS_EINVAL, "this blend variant is a development form that is not in this build (make EXPERIMENTS=1)");
 	}
 #endif
-	const bool use_split = !want_fused && (variant == 0 || variant == 14 || variant == 15 || variant >= 16) && !out_depth && num_channels >= 128 && L > 0;
+	// fp16 tables rendered by px4 + px1 instead of the sweep: variant 15, the norm plane, and rows the sweep's 16-byte LDS-DMA pieces cannot
+	// take aligned (C % 8 != 0, or a table that does not start on 16 bytes) -- those render as the fp32 table does under variant 6
+	const bool f16_px4 = feat_f16 && (variant == 15 || norm_plane || (num_channels & 7) != 0 || ((uintptr_t)colors_precomp & 15u) != 0);
+	const bool use_split = !want_fused && !f16_px4 && (variant == 0 || variant == 14 || variant == 15 || variant >= 16) && !out_depth && num_channels >= 128 && L > 0;
 	uint32_t arena_cap = 0;
 	uint64_t arena_max = 0;
 	if (use_split) {
@@ -934,7 +954,8 @@ int sgs_rasterize_forward(sgs_alloc_fn geometry_buffer, void* geometry_user,
 	a.gx = gx;
 	a.gy = gy;
 	a.means2D = means2D;
-	a.features = colors_precomp ? colors_precomp : rgb;
+	a.features = colors_precomp ? (const void*)colors_precomp : (const void*)rgb;
+	a.fmt = feat_f16 ? 1 : 0;
 	a.conic_opacity = conic_opacity;
 	a.depths = depths;
 	a.bg = background;
@@ -964,7 +985,13 @@ int sgs_rasterize_forward(sgs_alloc_fn geometry_buffer, void* geometry_user,
 		e = sgs::launch_blend_forward_fused(st, a, (variant & 0xff) == 33, ((variant >> 8) & 15) * 2);
 	} else
 #endif
-	if (norm_plane && (!use_split || want_fused)) {
+	if (norm_plane && f16_px4 && L > 0) {
+		// fp16 features: the norm plane from the px4 form's epilogue (its atomics add into a cleared plane)
+		tm.mark();
+		e = hipMemsetAsync(out_color, 0, (size_t)height * a.pitch * sizeof(float), st);
+		if (e != hipSuccess) return fail_hip(e, "memset (norm plane)");
+		e = sgs::launch_blend_forward(st, a, 0);
+	} else if (norm_plane && (!use_split || want_fused)) {
 		// nothing rendered (L == 0) -> every pixel is the background: sum_c bg[c]^2; any other reason is a variant
 		// that has no norm epilogue
 		if (L > 0) return fail(SGS_EINVAL, "SGS_OPT_NORM_PLANE needs the default blend (variants 0 / 15)");

@@ -98,7 +98,7 @@ struct BlendFwdArgs {
 	int W, H, C;
 	int gx, gy;
 	const float2* means2D;
-	const float* features;       // (P,C) row-major
+	const void* features;        // (P,C) row-major, elements of `fmt`
 	const float4* conic_opacity;
 	const float* depths;         // per Gaussian view z (RGB-D variant)
 	const float* bg;             // (C)
@@ -117,6 +117,8 @@ struct BlendFwdArgs {
 	// every frame rewrites it from the frame's own counts.
 	uint32_t* tile_order = nullptr;
 	int bands = 0;               // SGS_OPT_OUT_BANDS: > 1 = `out` is written band-major for that many image bands (sgs_band_of, sgs_device.h)
+	int fmt = 0;                 // SGS_OPT_FEATURE_FORMAT: 0 = fp32 features, 1 = fp16 (converted to fp32 on load; bg and the output stay fp32)
+	const float* features_f32() const { return static_cast<const float*>(features); }
 };
 // gate: optional device word; when non-null the 128-channel-aligned kernels exit unless
 // *gate != 0 (used as the arena-overflow fallback of the split path).

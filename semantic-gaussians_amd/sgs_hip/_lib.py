@@ -48,6 +48,7 @@ OPT_BLEND_VARIANT, OPT_BINNING_MODE, OPT_BACKWARD_MODE, OPT_STAGE_TIMING, OPT_OU
 OPT_OUT_BANDS = 8
 OPT_BWD_CLEARS_DCOLOR = 6
 OPT_NORM_PLANE = 7
+OPT_FEATURE_FORMAT = 9   # one shot: 0 = fp32 colors_precomp, 1 = fp16 (include/sgs_raster.h)
 STAT_ARENA_SLOTS, STAT_FWD_OVERFLOWS, STAT_BWD_OVERFLOWS, STAT_FORWARDS, STAT_DEFERRED_FORWARDS, STAT_DEFERRED_RETRIES, STAT_BWD_POOL_FALLBACKS, STAT_TILE_ORDER_ALLOC_FAILURES = 0, 1, 2, 3, 4, 5, 6, 7
 ERETRY, ENOTREADY = -5, -6
 

@@ -154,7 +154,15 @@ def _tracks_grad(*tensors):
 
 def rasterize_gaussians_chn(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                             cov3Ds_precomp, raster_settings):
+    """colors_precomp may be a float16 (P, C) table (what the reference's fusion.py saves): an inference frame reads it as it
+    is (SGS_OPT_FEATURE_FORMAT; the map is bit-identical to rendering the table's fp32 upcast, which is never made -- for C < 128 or
+    C % 8 == 0, see include/sgs_raster.h for other C).  A frame that
+    will be differentiated upcasts it with .float() INSIDE the autograd graph -- a (P, C) fp32 copy for the life of the frame
+    (2 GB at 1M x 512), as if the caller had passed fp32 -- so that the backward reads fp32 as ever and a half leaf gets a half
+    gradient."""
     track = _tracks_grad(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+    if track and isinstance(colors_precomp, torch.Tensor) and colors_precomp.dtype == torch.float16:
+        colors_precomp = colors_precomp.float()
     return _ChnFunction.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                               cov3Ds_precomp, raster_settings, track)
 

@@ -224,7 +224,10 @@ def rasterize_forward(background, means3D, colors, opacity, scales, rotations, s
     norm_plane: out_color is the (H,W) plane sum_c render[c]^2 instead of the (C,H,W) render (SGS_OPT_NORM_PLANE,
     include/sgs_raster.h; C % 128 == 0, inference only).
     out_bands = n > 1: out_color is a LIST of n contiguous (C, rows_b, W) tensors, the image bands of sgs_hip.dist.band_rows (views of one
-    buffer the kernels wrote band-major, SGS_OPT_OUT_BANDS; C % 128 == 0, no depth): each band is one message of an image-partitioned exchange."""
+    buffer the kernels wrote band-major, SGS_OPT_OUT_BANDS; C % 128 == 0, no depth): each band is one message of an image-partitioned exchange.
+    colors may be float16 when want_depth is false (SGS_OPT_FEATURE_FORMAT): the table is read as it is, converted to fp32 on load --
+    the map is bit-identical to rendering colors.float(), which is never made (C < 128 or C % 8 == 0; other C render on the px4 kernel,
+    bit-identical to colors.float() under blend variant 6: include/sgs_raster.h SGS_OPT_FEATURE_FORMAT)."""
     lib = _lib.load()
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -265,10 +268,13 @@ def rasterize_forward(background, means3D, colors, opacity, scales, rotations, s
         if want_depth:
             depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
 
-        def p(t, name):
-            ptr, kept = _ptr(t, name, dev)
+        def p(t, name, dtype=torch.float32):
+            ptr, kept = _ptr(t, name, dev, dtype)
             keep.append(kept)
             return ptr
+
+        # an fp16 feature table is passed through as it is (N-channel maps only; every other dtype keeps _ptr's message)
+        half = (colors is not None and colors.numel() != 0 and colors.dtype == torch.float16 and not want_depth)
 
         bg = _check_bg(background, Cn)
         M = sh.size(1) if (sh is not None and sh.numel() != 0) else 0
@@ -276,7 +282,7 @@ def rasterize_forward(background, means3D, colors, opacity, scales, rotations, s
         # library consumes the override in that call, the finally covers a failure inside ctypes itself
         args = (*bufs.callback("g"), *bufs.callback("b"), *bufs.callback("i"),
                 P, int(degree), int(M), p(bg, "bg"), W, H, p(means3D, "means3D"), p(sh, "sh"),
-                p(colors, "colors_precomp"), p(opacity, "opacities"), p(scales, "scales"),
+                p(colors, "colors_precomp", torch.float16 if half else torch.float32), p(opacity, "opacities"), p(scales, "scales"),
                 float(scale_modifier), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"),
                 p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix"), p(campos, "campos"),
                 float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), Cn, color.data_ptr(),
@@ -289,9 +295,13 @@ def rasterize_forward(background, means3D, colors, opacity, scales, rotations, s
                 lib.sgs_stream_set_option(_stream_ptr(dev), _lib.OPT_NORM_PLANE, 1)
             if out_bands > 1:
                 lib.sgs_stream_set_option(_stream_ptr(dev), _lib.OPT_OUT_BANDS, int(out_bands))
+            if half:
+                lib.sgs_stream_set_option(_stream_ptr(dev), _lib.OPT_FEATURE_FORMAT, 1)
             rc = lib.sgs_rasterize_forward(*args)
         finally:
             bufs.release()
+            if half:
+                lib.sgs_stream_set_option(_stream_ptr(dev), _lib.OPT_FEATURE_FORMAT, -1)
             if out_bands > 1:
                 lib.sgs_stream_set_option(_stream_ptr(dev), _lib.OPT_OUT_BANDS, -1)
             if pitch != W:

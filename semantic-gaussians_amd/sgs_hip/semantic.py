@@ -26,10 +26,21 @@ import torch
 from . import api, raster
 
 
+# rows of an fp16 table upcast at a time by project_features (64k x 768 x 4 B = 192 MB of fp32 at most)
+PROJECT_ROWS = 65536
+
+
 def project_features(features, text_features):
     """(P,C) Gaussian features x (n_cls,C) text embeddings -> (P,n_cls) per-Gaussian similarities.
-    Once per (scene, text set); one GEMM."""
-    return (features @ text_features.t()).contiguous()
+    Once per (scene, text set); one GEMM.  An fp16 table (what the reference's fusion.py saves) gives the fp32 projection of its
+    upcast, PROJECT_ROWS rows at a time: no (P,C) fp32 copy of the table is made."""
+    if features.dtype != torch.float16:
+        return (features @ text_features.t()).contiguous()
+    t = text_features.float().t()
+    out = torch.empty(features.shape[0], text_features.shape[0], dtype=torch.float32, device=features.device)
+    for i in range(0, features.shape[0], PROJECT_ROWS):
+        torch.matmul(features[i:i + PROJECT_ROWS].float(), t, out=out[i:i + PROJECT_ROWS])
+    return out
 
 
 def render_logits(raster_settings, means3D, opacities, scales, rotations, projected, text_features):
@@ -53,7 +64,7 @@ def labels_from_logits(logits, skip_first=True):
 
 def render_norm2(raster_settings, means3D, opacities, scales, rotations, features):
     """(H,W) plane  sum_c render[c]^2  of the C-channel feature render, without writing the render
-    (C % 128 == 0; inference only -- no autograd)."""
+    (C % 128 == 0; inference only -- no autograd).  `features` may be an fp16 table: it is read as it is."""
     s = raster_settings
     empty = torch.Tensor([])
     with torch.no_grad():
@@ -69,7 +80,8 @@ def render_similarity(raster_settings, means3D, opacities, scales, rotations, fe
     """(n_cls,H,W) similarities.  normalised=False: the projected render (fast path, argmax-equivalent).
     normalised=True: the reference's values (eval_segmentation.py:155-156): the projected render divided by the
     per-pixel norm of the full feature vector (render_norm2; C % 128 != 0 falls back to rendering the map).
-    `projected` = project_features(features, text_features) if the caller keeps it across views."""
+    `projected` = project_features(features, text_features) if the caller keeps it across views.  `features` may be an fp16 table:
+    every render reads it as it is (no fp32 copy)."""
     if projected is None:
         projected = project_features(features, text_features)
     if not normalised:
