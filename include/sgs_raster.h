@@ -443,6 +443,40 @@ int sgs_fusion_compute_mapping(int N, const float *coords, const float *world_vi
 int sgs_fusion_accumulate(int N, int C, const float *features_hwc, int image_w, int image_h,
                           const long long *mapping, float *feat_sum, float *times, void *stream);
 
+/* The training loss of train.py:138-150 in one forward launch pair and one backward launch (photometric_loss.hip):
+ *     loss = (1 - lambda) * mean|img - gt| + lambda * (1 - SSIM(img, gt))
+ * with SSIM as utils/loss_utils.py builds it: 11-tap Gaussian window (sigma 1.5, normalised, rounded to fp32 as
+ * gaussian(11, 1.5) rounds it), zero padding of 5, C1 = 0.01^2, C2 = 0.03^2, mean over all entries.
+ *
+ *   B, C, H, W            images, channels, rows, columns (all > 0)
+ *   img, gt               float32, device.  Entry (b, c, y, x) is at  base[b * image_pitch + c * channel_pitch + y * row_pitch + x]
+ *                         (pitches in ELEMENTS, row_pitch >= W): a crop of a larger image is read in place
+ *   mean_over_batch       1: one mean over all B images (the outputs / grad_loss have 1 entry); 0: one per image (B entries)
+ *   out_loss, out_l1      float32, device.  out_l1 may be NULL
+ *   out_ssim              float32, device; NULL with lambda == 0 is the L1-only form (no window is evaluated)
+ *   dmaps                 NULL, or 3 * B*C*H*W float32: the per-pixel derivatives of the SSIM map by mu1, sigma1^2 and sigma12
+ *                         that the backward filters.  NULL: nothing is stored (no gradient will be asked for)
+ *   scratch               sgs_photometric_loss_scratch_bytes(B, C, H, W) bytes, device, 8-byte aligned: one pair of float64 sums per
+ *                         32x32 tile.  They are added in a fixed order (no floating-point atomics): the outputs are the same bits on every run
+ *
+ * sgs_photometric_loss_backward writes the contiguous (B, C, H, W) gradient by img of
+ *     w_ssim * SSIM(img, gt) + w_l1 * mean|img - gt|,   times the upstream gradient grad_loss (DEVICE memory, 1 or B entries; never read on
+ * the host).  The loss above is w_ssim = -lambda, w_l1 = 1 - lambda.  dmaps == NULL needs w_ssim == 0.  sign(0) = 0 as in torch's abs backward.
+ *
+ * sgs_photometric_loss_window: the 11 taps, host only.  Bad sizes, null images and row_pitch < W are SGS_EINVAL before any device work. */
+long long sgs_photometric_loss_scratch_bytes(int B, int C, int H, int W);
+int sgs_photometric_loss_window(float *taps11);
+int sgs_photometric_loss_forward(int B, int C, int H, int W,
+                                 const float *img, long long img_row_pitch, long long img_channel_pitch, long long img_image_pitch,
+                                 const float *gt, long long gt_row_pitch, long long gt_channel_pitch, long long gt_image_pitch,
+                                 float lambda, int mean_over_batch, float *out_loss, float *out_ssim, float *out_l1,
+                                 float *dmaps, void *scratch, size_t scratch_bytes, void *stream);
+int sgs_photometric_loss_backward(int B, int C, int H, int W,
+                                  const float *img, long long img_row_pitch, long long img_channel_pitch, long long img_image_pitch,
+                                  const float *gt, long long gt_row_pitch, long long gt_channel_pitch, long long gt_image_pitch,
+                                  float w_ssim, float w_l1, const float *dmaps, const float *grad_loss, int mean_over_batch,
+                                  float *out_grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1281,6 +1281,60 @@ int sgs_fusion_accumulate(int N, int C, const float* features_hwc, int image_w, 
 	return 0;
 }
 
+static int loss_args_ok(int B, int C, int H, int W, const float* img, long long img_row, const float* gt, long long gt_row)
+{
+	if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(SGS_EINVAL, "photometric loss: bad sizes (B, C, H, W must be positive)");
+	if ((long long)B * C > 65535) return fail(SGS_EINVAL, "photometric loss: more than 65535 (image, channel) planes");
+	if (!img || !gt) return fail(SGS_EINVAL, "photometric loss: null image");
+	if (img_row < W || gt_row < W) return fail(SGS_EINVAL, "photometric loss: row pitch smaller than the image width");
+	return 0;
+}
+
+long long sgs_photometric_loss_scratch_bytes(int B, int C, int H, int W)
+{
+	if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(SGS_EINVAL, "photometric loss: bad sizes (B, C, H, W must be positive)");
+	return (long long)sgs::photometric_loss_scratch_bytes(B, C, H, W);
+}
+
+int sgs_photometric_loss_window(float* taps11)
+{
+	if (!taps11) return fail(SGS_EINVAL, "null argument");
+	sgs::photometric_loss_taps(taps11);
+	return 0;
+}
+
+int sgs_photometric_loss_forward(int B, int C, int H, int W, const float* img, long long img_row_pitch, long long img_channel_pitch,
+				 long long img_image_pitch, const float* gt, long long gt_row_pitch, long long gt_channel_pitch,
+				 long long gt_image_pitch, float lambda, int mean_over_batch, float* out_loss, float* out_ssim, float* out_l1,
+				 float* dmaps, void* scratch, size_t scratch_bytes, void* stream)
+{
+	if (int rc = loss_args_ok(B, C, H, W, img, img_row_pitch, gt, gt_row_pitch)) return rc;
+	if (!out_loss) return fail(SGS_EINVAL, "photometric loss: null output");
+	if (!out_ssim && (lambda != 0.f || dmaps)) return fail(SGS_EINVAL, "photometric loss: out_ssim may be NULL only with lambda == 0 and no derivative maps");
+	if (!scratch || scratch_bytes < sgs::photometric_loss_scratch_bytes(B, C, H, W) || ((uintptr_t)scratch & 7u))
+		return fail(SGS_EINVAL, "photometric loss: scratch is null, misaligned or smaller than sgs_photometric_loss_scratch_bytes()");
+	const long long ip[3] = {img_row_pitch, img_channel_pitch, img_image_pitch}, gp[3] = {gt_row_pitch, gt_channel_pitch, gt_image_pitch};
+	hipError_t e = sgs::launch_photometric_loss_forward((hipStream_t)stream, B, C, H, W, img, ip, gt, gp, lambda, mean_over_batch != 0,
+							    out_loss, out_ssim, out_l1, dmaps, scratch);
+	if (e != hipSuccess) return fail_hip(e, "photometric loss forward");
+	return 0;
+}
+
+int sgs_photometric_loss_backward(int B, int C, int H, int W, const float* img, long long img_row_pitch, long long img_channel_pitch,
+				  long long img_image_pitch, const float* gt, long long gt_row_pitch, long long gt_channel_pitch,
+				  long long gt_image_pitch, float w_ssim, float w_l1, const float* dmaps, const float* grad_loss,
+				  int mean_over_batch, float* out_grad, void* stream)
+{
+	if (int rc = loss_args_ok(B, C, H, W, img, img_row_pitch, gt, gt_row_pitch)) return rc;
+	if (!grad_loss || !out_grad) return fail(SGS_EINVAL, "photometric loss: null gradient buffer");
+	if (!dmaps && w_ssim != 0.f) return fail(SGS_EINVAL, "photometric loss: the SSIM term's gradient needs the forward's derivative maps");
+	const long long ip[3] = {img_row_pitch, img_channel_pitch, img_image_pitch}, gp[3] = {gt_row_pitch, gt_channel_pitch, gt_image_pitch};
+	hipError_t e = sgs::launch_photometric_loss_backward((hipStream_t)stream, B, C, H, W, img, ip, gt, gp, w_ssim, w_l1, dmaps, grad_loss,
+							     mean_over_batch != 0, out_grad);
+	if (e != hipSuccess) return fail_hip(e, "photometric loss backward");
+	return 0;
+}
+
 int sgs_composite_over(int num_shards, const float* const* partial_A, const float* const* partial_T, const float* background,
 		       float* out, float* T_out, int num_channels, int rows, int width, void* stream)
 {

@@ -243,4 +243,15 @@ hipError_t launch_fusion_mapping(hipStream_t st, int N, const float* coords, con
 hipError_t launch_fusion_accumulate(hipStream_t st, int N, int C, const float* feat_hwc, int W,
 				    const long long* mapping, float* feat_sum, float* times);
 
+// ---- photometric_loss.hip: (1 - lambda) * L1 + lambda * (1 - SSIM), forward and backward (train.py:138-150, utils/loss_utils.py)
+// pitches: {row, channel, image} in elements.  out_ssim == NULL: L1 only.  dmaps == NULL: no derivative maps / no SSIM term.
+size_t photometric_loss_scratch_bytes(int B, int C, int H, int W);
+void photometric_loss_taps(float out[11]);
+hipError_t launch_photometric_loss_forward(hipStream_t st, int B, int C, int H, int W, const float* img, const long long img_pitch[3],
+					   const float* gt, const long long gt_pitch[3], float lambda, int mean_over_batch, float* out_loss,
+					   float* out_ssim, float* out_l1, float* dmaps, void* scratch);
+hipError_t launch_photometric_loss_backward(hipStream_t st, int B, int C, int H, int W, const float* img, const long long img_pitch[3],
+					    const float* gt, const long long gt_pitch[3], float w_ssim, float w_l1, const float* dmaps,
+					    const float* grad_loss, int mean_over_batch, float* out_grad);
+
 } // namespace sgs

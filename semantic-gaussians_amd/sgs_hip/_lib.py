@@ -41,6 +41,7 @@ EXPORTS = (
     "sgs_stream_set_option", "sgs_stream_get_stat", "sgs_stream_release", "sgs_debug_set_sweep_trace",
     "sgs_forward_result", "sgs_debug_depth_sort",
     "sgs_device_cu_count", "sgs_stream_create_cu_range", "sgs_stream_destroy", "sgs_stream_set_front", "sgs_x16_cu_ownership",
+    "sgs_photometric_loss_scratch_bytes", "sgs_photometric_loss_window", "sgs_photometric_loss_forward", "sgs_photometric_loss_backward",
 )
 
 # sgs_stream_set_option / sgs_stream_get_stat selectors (include/sgs_raster.h)
@@ -151,6 +152,15 @@ def load():
     lib.sgs_stream_set_front.argtypes = [p, p]
     lib.sgs_x16_cu_ownership.restype = i
     lib.sgs_x16_cu_ownership.argtypes = []
+    ll = C.c_longlong
+    lib.sgs_photometric_loss_scratch_bytes.restype = ll
+    lib.sgs_photometric_loss_scratch_bytes.argtypes = [i, i, i, i]
+    lib.sgs_photometric_loss_window.restype = i
+    lib.sgs_photometric_loss_window.argtypes = [C.POINTER(f)]
+    lib.sgs_photometric_loss_forward.restype = i
+    lib.sgs_photometric_loss_forward.argtypes = [i, i, i, i, p, ll, ll, ll, p, ll, ll, ll, f, i, p, p, p, p, p, C.c_size_t, p]
+    lib.sgs_photometric_loss_backward.restype = i
+    lib.sgs_photometric_loss_backward.argtypes = [i, i, i, i, p, ll, ll, ll, p, ll, ll, ll, f, f, p, p, i, p, p]
     _lib = lib
     return lib
 

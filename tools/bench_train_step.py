@@ -1,7 +1,10 @@
 """N2 measurement: one optimisation step as train.py runs it (render -> L1 -> backward -> Adam) at cfg2
 (500k Gaussians, RGB-D rasteriser, 968x1296), and the same with a 512-channel feature target at cfg3's size
-(distillation-style; the reference's backward cannot run this)."""
-import os, sys, time
+(distillation-style; the reference's backward cannot run this).  A second cfg2 line runs the step with the loss train.py actually
+trains with, (1 - lambda) * L1 + lambda * (1 - SSIM) (train.py:149), once through sgs_hip.loss.photometric_loss and once composed from
+torch ops (tools/bench_photometric_loss.py composed_loss).  Every figure is the median of 5 timings of N iterations, each a host clock
+around work that ends in a device synchronise, after 3 warm-up iterations."""
+import os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "semantic-gaussians_amd"))
 import torch
@@ -9,6 +12,8 @@ import rgbd_rasterization as rr
 import channel_rasterization as cr
 from sgs_hip.synthetic import CONFIGS, make_scene
 from sgs_hip.camera import pinhole
+from sgs_hip.loss import photometric_loss
+from bench_photometric_loss import composed_loss, gaussian_window
 
 dev = "cuda:0"
 for name, C in (("cfg2", 3), ("cfg3", 512)):
@@ -30,22 +35,33 @@ for name, C in (("cfg2", 3), ("cfg3", 512)):
     opt = torch.optim.Adam([xyz, colors, opacity, scaling, rotation], lr=1e-4, eps=1e-15)
     target = torch.rand(C, H, W, device=dev)
 
-    def step():
+    losses = {"L1": lambda image: (image - target).abs().mean()}
+    if name == "cfg2":
+        window = gaussian_window(3, dev)
+        losses["L1 + D-SSIM (sgs_hip.loss.photometric_loss)"] = lambda image: photometric_loss(image, target, 0.2)
+        losses["L1 + D-SSIM (composed from torch ops)"] = lambda image: composed_loss(image, target, 0.2, window)
+
+    def step(loss_fn):
         m2d = torch.zeros_like(xyz, requires_grad=True) + 0
         out = rast(means3D=xyz, means2D=m2d, shs=None, colors_precomp=colors, opacities=torch.sigmoid(opacity),
                    scales=torch.exp(scaling), rotations=torch.nn.functional.normalize(rotation), cov3D_precomp=None)
-        loss = (out[0] - target).abs().mean()
+        loss = loss_fn(out[0])
         loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
 
     N = 20 if C == 3 else 5
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(N):
-        step()
-    torch.cuda.synchronize()
-    t = (time.perf_counter() - t0) / N
-    print(f"{name} P={P} C={C} {W}x{H}: render + L1 + backward + Adam = {t * 1e3:.2f} ms per iteration ({1 / t:.0f} it/s)")
+    for what, loss_fn in losses.items():
+        for _ in range(3):
+            step(loss_fn)
+        ts = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(N):
+                step(loss_fn)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / N)
+        t = statistics.median(ts)
+        print(f"{name} P={P} C={C} {W}x{H}: render + {what} + backward + Adam = {t * 1e3:.2f} ms per iteration ({1 / t:.0f} it/s)"
+              f"  [min {min(ts) * 1e3:.2f}, max {max(ts) * 1e3:.2f}]")
