@@ -477,6 +477,44 @@ int sgs_photometric_loss_backward(int B, int C, int H, int W,
                                   float w_ssim, float w_l1, const float *dmaps, const float *grad_loss, int mean_over_batch,
                                   float *out_grad, void *stream);
 
+/* The rest of an optimisation step after loss.backward() (optim.hip; replaces torch.optim.Adam.step as train.py:179 uses it, and
+ * train.py:158-161 + model/gaussian_model.py:608-612).
+ *
+ * sgs_adam_step: torch.optim.Adam's update (no amsgrad, weight_decay = 0) of `n` float32 tensors in ceil(non-empty / sgs_adam_max_tensors())
+ * launches -- one for the reference's six groups.  The descriptors travel in the kernel arguments: no copy, no synchronisation.
+ *   param, grad, exp_avg, exp_avg_sq   float32, device, contiguous, numel entries each; updated in place (grad is read only).  Tensors whose
+ *                         four pointers are all 16-byte aligned move 16 bytes per access, others go by element
+ *   rows, numel           leading size and entry count (numel % rows == 0; width = numel / rows).  rows == 0 or numel == 0: nothing to do
+ *   lr, beta1, beta2, eps, step   this tensor's hyper-parameters and its step count t >= 1 INCLUDING this step
+ *   visible               NULL, or `rows` bytes (uint8 / bool, device): entries of a row with visible[row] == 0 are neither read nor
+ *                         written.  With a mask every tensor must have the same `rows`
+ * Arithmetic: seven scalars derived in double and rounded once to float32
+ *     b1 = beta1, c1 = 1 - beta1, b2 = beta2, c2 = 1 - beta2, r = sqrt(1 - beta2^t), e = eps, s = lr / (1 - beta1^t)
+ * then per entry, every operation a separate correctly rounded float32 operation:
+ *     m' = (b1*m) + (c1*g);   v' = (b2*v) + (c2*(g*g));   den = (sqrtf(v') / r) + e;   p' = p - (s * (m' / den))
+ * Returns the number of kernel launches (>= 0), or a negative code + sgs_last_error() before anything is launched.
+ *
+ * sgs_adam_max_tensors: tensors per launch (>= 8), host only.
+ *
+ * sgs_densify_stats: per Gaussian i < P that is visible -- visible_in[i] != 0, or radii[i] > 0 when visible_in is NULL:
+ *     accum[i] += sqrtf((gx*gx) + (gy*gy));  denom[i] += 1;  max_radii2D[i] = fmaxf(max_radii2D[i], (float)radii[i])
+ * with (gx, gy) = viewspace_grad[i * grad_row_pitch + 0 / 1] (pitch in elements, >= 2).  visible_out (NULL or P bytes) receives the
+ * condition as 0 / 1: the mask for sgs_adam_step.  One launch, no host read. */
+typedef struct sgs_adam_tensor {
+	float *param;
+	const float *grad;
+	float *exp_avg;
+	float *exp_avg_sq;
+	long long rows;
+	long long numel;
+	double lr, beta1, beta2, eps;
+	int64_t step;
+} sgs_adam_tensor;
+int sgs_adam_step(const sgs_adam_tensor *tensors, int n, const uint8_t *visible, void *stream);
+int sgs_adam_max_tensors(void);
+int sgs_densify_stats(int P, const float *viewspace_grad, long long grad_row_pitch, const int *radii, const uint8_t *visible_in,
+                      float *accum, float *denom, float *max_radii2D, uint8_t *visible_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 #include "sgs_kernels.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1332,6 +1333,80 @@ int sgs_photometric_loss_backward(int B, int C, int H, int W, const float* img, 
 	hipError_t e = sgs::launch_photometric_loss_backward((hipStream_t)stream, B, C, H, W, img, ip, gt, gp, w_ssim, w_l1, dmaps, grad_loss,
 							     mean_over_batch != 0, out_grad);
 	if (e != hipSuccess) return fail_hip(e, "photometric loss backward");
+	return 0;
+}
+
+int sgs_adam_max_tensors(void) { return SGS_ADAM_MAX_TENSORS; }
+
+int sgs_adam_step(const sgs_adam_tensor* tensors, int n, const uint8_t* visible, void* stream)
+{
+	if (n < 0 || (n > 0 && !tensors)) return fail(SGS_EINVAL, "adam: bad tensor list");
+	const long long chunk = sgs::adam_chunk_elements();
+	// everything is checked before the first launch
+	for (int k = 0; k < n; ++k) {
+		const sgs_adam_tensor& d = tensors[k];
+		const std::string who = "adam: tensor " + std::to_string(k) + ": ";
+		if (d.rows < 0 || d.numel < 0 || (d.rows == 0 && d.numel != 0) || (d.rows > 0 && d.numel % d.rows != 0))
+			return fail(SGS_EINVAL, who + "bad sizes (numel must be a multiple of rows)");
+		if (visible && d.rows != tensors[0].rows) return fail(SGS_EINVAL, who + "a visibility mask needs the same number of rows in every tensor");
+		if (d.numel == 0) continue;
+		if (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq) return fail(SGS_EINVAL, who + "null pointer");
+		if (((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq) & 3u)
+			return fail(SGS_EINVAL, who + "pointer not aligned to 4 bytes");
+		if (d.step < 1) return fail(SGS_EINVAL, who + "step must be >= 1 (the count including this step)");
+		if (!(d.beta1 >= 0.0 && d.beta1 < 1.0 && d.beta2 >= 0.0 && d.beta2 < 1.0) || !(d.eps >= 0.0) || !std::isfinite(d.lr))
+			return fail(SGS_EINVAL, who + "bad hyper-parameters (betas in [0, 1), eps >= 0, finite lr)");
+		if (visible && d.numel / d.rows > 0x7fffffffll - chunk) return fail(SGS_EINVAL, who + "rows wider than 2^31 - 1024 entries cannot take a mask");
+		// (a launch counts the chunks of its tensors in one int)
+		if ((d.numel + chunk - 1) / chunk > 0x7fffffffll / SGS_ADAM_MAX_TENSORS) return fail(SGS_EINVAL, who + "too large for one launch");
+	}
+	int launches = 0, k = 0;
+	while (k < n) {
+		sgs::AdamTable tab = {};
+		tab.visible = visible;
+		long long chunks = 0;
+		for (; k < n && tab.n < SGS_ADAM_MAX_TENSORS; ++k) {
+			const sgs_adam_tensor& d = tensors[k];
+			if (d.numel == 0) continue;
+			sgs::AdamTensor& t = tab.t[tab.n];
+			t.param = d.param;
+			t.grad = d.grad;
+			t.exp_avg = d.exp_avg;
+			t.exp_avg_sq = d.exp_avg_sq;
+			t.numel = d.numel;
+			t.width = (unsigned)(d.numel / d.rows);
+			t.vec4 = ((((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq) & 15u) == 0) ? 1 : 0;
+			const double bc1 = 1.0 - std::pow(d.beta1, (double)d.step), bc2 = 1.0 - std::pow(d.beta2, (double)d.step);
+			t.b1 = (float)d.beta1;
+			t.c1 = (float)(1.0 - d.beta1);
+			t.b2 = (float)d.beta2;
+			t.c2 = (float)(1.0 - d.beta2);
+			t.r = (float)std::sqrt(bc2);
+			t.e = (float)d.eps;
+			t.s = (float)(d.lr / bc1);
+			tab.chunk_start[tab.n] = (int)chunks;
+			chunks += (d.numel + chunk - 1) / chunk;
+			++tab.n;
+		}
+		if (tab.n == 0) continue;
+		tab.chunk_start[tab.n] = (int)chunks;
+		hipError_t e = sgs::launch_adam_multi((hipStream_t)stream, tab);
+		if (e != hipSuccess) return fail_hip(e, "adam step");
+		++launches;
+	}
+	return launches;
+}
+
+int sgs_densify_stats(int P, const float* viewspace_grad, long long grad_row_pitch, const int* radii, const uint8_t* visible_in,
+		      float* accum, float* denom, float* max_radii2D, uint8_t* visible_out, void* stream)
+{
+	if (P < 0) return fail(SGS_EINVAL, "densify stats: bad size");
+	if (P == 0) return 0;
+	if (!viewspace_grad || !radii || !accum || !denom || !max_radii2D) return fail(SGS_EINVAL, "densify stats: null argument");
+	if (grad_row_pitch < 2) return fail(SGS_EINVAL, "densify stats: the gradient's row pitch must hold two entries");
+	hipError_t e = sgs::launch_densify_stats((hipStream_t)stream, P, viewspace_grad, grad_row_pitch, radii, visible_in, accum, denom,
+						 max_radii2D, visible_out);
+	if (e != hipSuccess) return fail_hip(e, "densify stats");
 	return 0;
 }
 

@@ -254,4 +254,30 @@ hipError_t launch_photometric_loss_backward(hipStream_t st, int B, int C, int H,
 					    const float* gt, const long long gt_pitch[3], float w_ssim, float w_l1, const float* dmaps,
 					    const float* grad_loss, int mean_over_batch, float* out_grad);
 
+// ---- optim.hip: Adam over several tensors in one launch (optional row mask) and the densification statistics (train.py:154-180)
+#define SGS_ADAM_MAX_TENSORS 16
+// one tensor of a launch.  vec4: all four pointers are 16-byte aligned (float4 path).  width = numel / rows (read under a mask only).
+// b1 .. s: the seven float32 scalars of the arithmetic contract (optim.hip), derived on the host in double and rounded once.
+struct AdamTensor {
+	float* param;
+	const float* grad;
+	float* exp_avg;
+	float* exp_avg_sq;
+	long long numel;
+	unsigned width;
+	int vec4;
+	float b1, c1, b2, c2, r, e, s;
+};
+// the kernel's by-value argument: chunk_start[k] = chunks (of adam_chunk_elements() elements) before tensor k, chunk_start[n] = all
+struct AdamTable {
+	AdamTensor t[SGS_ADAM_MAX_TENSORS];
+	int chunk_start[SGS_ADAM_MAX_TENSORS + 1];
+	int n;
+	const uint8_t* visible;   // NULL: dense
+};
+int adam_chunk_elements();
+hipError_t launch_adam_multi(hipStream_t st, const AdamTable& tab);
+hipError_t launch_densify_stats(hipStream_t st, int P, const float* viewspace_grad, long long grad_row_pitch, const int* radii,
+				const uint8_t* visible_in, float* accum, float* denom, float* max_radii2D, uint8_t* visible_out);
+
 } // namespace sgs

@@ -28,6 +28,13 @@ class BinningLayout(C.Structure):
         "keys_unsorted", "vals_unsorted", "keys_sorted", "point_list", "total")]
 
 
+class AdamTensor(C.Structure):
+    """sgs_adam_tensor (include/sgs_raster.h)"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("rows", C.c_longlong), ("numel", C.c_longlong),
+                ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("step", C.c_int64)]
+
+
 class ImageLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("accum_alpha", "n_contrib", "ranges", "total")]
 
@@ -42,6 +49,7 @@ EXPORTS = (
     "sgs_forward_result", "sgs_debug_depth_sort",
     "sgs_device_cu_count", "sgs_stream_create_cu_range", "sgs_stream_destroy", "sgs_stream_set_front", "sgs_x16_cu_ownership",
     "sgs_photometric_loss_scratch_bytes", "sgs_photometric_loss_window", "sgs_photometric_loss_forward", "sgs_photometric_loss_backward",
+    "sgs_adam_step", "sgs_adam_max_tensors", "sgs_densify_stats",
 )
 
 # sgs_stream_set_option / sgs_stream_get_stat selectors (include/sgs_raster.h)
@@ -161,6 +169,12 @@ def load():
     lib.sgs_photometric_loss_forward.argtypes = [i, i, i, i, p, ll, ll, ll, p, ll, ll, ll, f, i, p, p, p, p, p, C.c_size_t, p]
     lib.sgs_photometric_loss_backward.restype = i
     lib.sgs_photometric_loss_backward.argtypes = [i, i, i, i, p, ll, ll, ll, p, ll, ll, ll, f, f, p, p, i, p, p]
+    lib.sgs_adam_step.restype = i
+    lib.sgs_adam_step.argtypes = [C.POINTER(AdamTensor), i, p, p]
+    lib.sgs_adam_max_tensors.restype = i
+    lib.sgs_adam_max_tensors.argtypes = []
+    lib.sgs_densify_stats.restype = i
+    lib.sgs_densify_stats.argtypes = [i, p, ll, p, p, p, p, p, p, p]
     _lib = lib
     return lib
 
